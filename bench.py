@@ -7,8 +7,13 @@ the reference DataLoader delivers them), batch 8 per GPU, weighted CE, bf16 comp
 fp32 master weights.  One step = general_step (forward + loss) + backward + gradient
 all-reduce (N>1) + Adam; all parameters trainable (lr_pretrained set).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...      (one process per GPU, RCCL)
+
+A plain run sets up, warms up, times the K steps and prints the result line.  ``--full`` adds
+the legs that take runs of their own (``roofline``, ``cpu_baseline``, below);
+``--dump-outputs DIR`` writes what the last timed step computed as ``DIR/<name>.npy``
+(``dump_outputs``), so that two builds can be compared output for output.
 
 The step is captured once as HIP graphs and replayed (``--eager`` launches it from Python
 every step).  Under torchrun (``--collectives``):
@@ -25,7 +30,7 @@ every step).  Under torchrun (``--collectives``):
     the node (tools/spin_contention.py: 16 CUs held through a step cost ~0.5 ms);
   * ``inside`` (``--graph``): the all-reduces captured inside the step graph.
 Rank 0 prints one JSON line.
-``roofline`` times the dominant kernel (layer4.0.conv2 forward, the lattice conv; ``frac`` on
+With ``--full``: ``roofline`` times the dominant kernel (layer4.0.conv2 forward, the lattice conv; ``frac`` on
 the MACs it executes, ``dense_frac`` on the dense count) and, under ``kernels``, also that
 conv's weight gradient (the largest single launch) with HIP events recorded around each of
 their launches, on the stream they run on -- inside the timed region when eager, over eager
@@ -60,6 +65,8 @@ M2_BYTES_PER_VOL = 1.163e9               # unfused eager byte model (SURVEY.md 8
 PEAK_BF16 = 2.5e15                       # MI355X dense bf16 MFMA (MI355X_MICROARCH.md)
 PEAK_F32 = 157.3e12
 PEAK_HBM = 8.0e12
+# --dump-outputs: parameters / gradients are written at this many seeded positions (16 MB)
+DUMP_SAMPLE, DUMP_SEED = 1 << 20, 0
 # --collectives modes with a graph_step form: (graph_step collectives, backward cuts)
 DP_MODES = {"staged": ("staged", DEFAULT_CUTS), "staged1": ("staged", ("layer3",)),
             "after": ("after", DEFAULT_CUTS)}
@@ -201,6 +208,36 @@ def cpu_baseline(size, budgets=((1, 10.0), (8, 16.0))):
                       f"threads ({'; '.join(samples)})"}
 
 
+def dump_outputs(path, out, model):
+    """``--dump-outputs``: what a caller of the timed step receives from its last call, one
+    ``<name>.npy`` each (float64 where the step computes in float64, float32 otherwise):
+    ``loss``, ``outputs`` (the logits) and ``labels`` as the step returns them, and what it
+    leaves on the model -- ``params_sample`` / ``grads_sample``, the updated trainable
+    parameters and their gradients (zeros where a parameter received none), flattened in
+    ``model.parameters()`` order and read at DUMP_SAMPLE fixed, seeded positions
+    (``sample_index``; every element when there are fewer)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    torch.cuda.synchronize()
+    arrays = {k: out[k].detach() for k in ("loss", "outputs", "labels")
+              if torch.is_tensor(out.get(k))}
+    params = [p for p in model.parameters() if p.requires_grad]
+    n = sum(p.numel() for p in params)
+    idx = torch.randperm(n, generator=torch.Generator().manual_seed(DUMP_SEED))
+    idx = idx[:DUMP_SAMPLE].sort().values
+    dev = idx.to(params[0].device)
+    arrays["sample_index"] = idx
+    arrays["params_sample"] = torch.cat([p.detach().reshape(-1) for p in params])[dev]
+    arrays["grads_sample"] = torch.cat([
+        (p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1)
+        for p in params])[dev]
+    for name, t in arrays.items():
+        t = t.cpu()
+        np.save(os.path.join(path, name + ".npy"),
+                t.to(torch.float64 if t.dtype in (torch.float64, torch.int64)
+                     else torch.float32).numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -211,8 +248,17 @@ def main():
                     help="cubic volume edge, or 'mni' for the reference's own 91x109x91 MNI "
                          "volumes (pkg/utils/dataloader.py:228-229; secondary line)")
     ap.add_argument("--precision", default="bf16")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beyond the headline figure: the dominant-kernel "
+                         "roofline probe (extra eager steps before the capture) and the CPU "
+                         "baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed as "
+                         "DIR/<name>.npy (dump_outputs; rank 0)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true",
+                    help="with --full: skip the roofline probe")
     ap.add_argument("--collectives", default="auto", choices=list(DP_MODES) + ["auto", "inside"],
                     help="under torchrun: how the gradient all-reduce meets the replayed step "
                          "(module docstring); auto probes staged / staged1 / after")
@@ -228,6 +274,9 @@ def main():
     args = ap.parse_args()
     mni = args.size == "mni"
     args.size = 128 if mni else int(args.size)
+    if not args.full:
+        args.no_roofline = True
+        args.no_cpu_baseline = True
     if mni:
         args.no_roofline = True           # the probe times the 128^3 dominant kernel
         args.no_cpu_baseline = True
@@ -299,11 +348,15 @@ def main():
         batch["tabular"] = torch.rand((B, 9), device="cuda", dtype=torch.float64, generator=g)
 
     dp_events = []                          # (start, end) around each timed finish()
+    last = {}                               # what the latest step returned (--dump-outputs)
 
     def step(timed=False):
         opt.zero_grad(set_to_none=True)
         out = model.general_step(batch, 0, "train")
         out["loss"].backward()
+        # detached: a live grad_fn chain would keep the AccumulateGrad nodes alive into the
+        # graph capture, which runs on another stream (graph_step.GraphedTrainStep)
+        last["out"] = {k: v.detach() if torch.is_tensor(v) else v for k, v in out.items()}
         if reducer is not None:
             if timed:
                 e0 = torch.cuda.Event(enable_timing=True)
@@ -373,7 +426,7 @@ def main():
 
         def step(timed=False):
             gstep.finish_events = dp_events if timed and reducer is not None else None
-            gstep()
+            last["out"] = gstep()
     else:
         for _ in range(args.warmup):
             step()
@@ -399,6 +452,8 @@ def main():
         el = t.item()
     ms = el / args.steps * 1e3
     value = world * B * args.steps / el
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, last["out"], model)
     cdtype = torch.bfloat16 if args.precision == "bf16" else torch.float32
     result = {
         "metric": "volumes/sec fwd+bwd, 3D-ResNet-10 @128^3 bf16, 1/2/4/8 MI355X; % HBM roofline",

@@ -25,5 +25,5 @@ if [ -n "$SEL" ]; then
 fi
 step prof 200 rocprofv3 --kernel-trace --stats -d $OUT/prof -o run --output-format csv -- python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-roofline
 python3 tools/prof_summary.py stepavg $OUT/prof > $OUT/step.txt 2>&1; cat $OUT/step.txt
-step bench 200 python -u bench.py --steps 20 --warmup 5 --no-cpu-baseline
+step bench 200 python -u bench.py --full --steps 20 --warmup 5 --no-cpu-baseline
 echo session done

@@ -17,8 +17,8 @@ step() {
 }
 step suite 600 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread
 step smoke 200 python -u -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')"
-step bench 240 python -u bench.py --steps 20 --warmup 5
-step prof 240 rocprofv3 --kernel-trace --stats -d $OUT/prof -o run --output-format csv -- python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline
+step bench 240 python -u bench.py --full --steps 20 --warmup 5
+step prof 240 rocprofv3 --kernel-trace --stats -d $OUT/prof -o run --output-format csv -- python3 bench.py --full --steps 10 --warmup 3 --no-cpu-baseline
 python3 tools/prof_summary.py stats $OUT/prof 40 > $OUT/stats.txt 2>&1
 python3 tools/prof_summary.py stepavg $OUT/prof > $OUT/step.txt 2>&1
 head -1 $OUT/step.txt

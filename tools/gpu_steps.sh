@@ -5,7 +5,7 @@
 # abort, signal or the time limit) ends the call there.
 #   gpurun -- 'bash tools/gpu_steps.sh r04a <<EOF
 #   tests 400 python -u -m pytest -v --timeout 200 --timeout-method thread tests/test_x_gpu.py
-#   bench 240 python -u bench.py --steps 20 --warmup 5
+#   bench 240 python -u bench.py --full --steps 20 --warmup 5
 #   EOF'
 # Named drivers: tools/gpu_final.sh (round-end validation), tools/gpu_check.sh (a kernel's
 # tests + step trace + bench), tools/gpu_workloads.sh (secondary workloads).
