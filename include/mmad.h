@@ -487,6 +487,45 @@ int mmad_mri_zscore_norm(int nscan, int64_t vox, const double* x, const double* 
 int mmad_affine_norm(int64_t n, const double* x, double mean, double stdv, double* out,
                      void* stream);
 
+/* ---- input pipeline augmentation (float64, batched over samples; no reference
+ * counterpart: the reference augments only through CPU transforms, transform_mri /
+ * transform_pet of pkg/utils/dataloader.py) ------------------------------------------
+ * Coordinates are those of torch's F.affine_grid / F.grid_sample with
+ * align_corners=False on a 5-D input: normalised (x, y, z) = (W, H, D), voxel centres at
+ * (2 i + 1) / size - 1.  theta [b][3][4] maps OUTPUT to INPUT coordinates.
+ *
+ * mmad_augment_draw: one thread per sample draws, from the device-resident seed (read
+ * when the kernel runs: a captured graph draws afresh on every replay),
+ *   flips f = -1 with probability flip_p, angles in +-rot_max, scale s in
+ *   [scale_lo, scale_hi], translations t in +-trans_max voxels, and per modality a gain
+ *   and a bias in their ranges; per-axis fields are in tensor order (d, h, w).
+ * Composed in voxel units, A = s Rz Ry Rx diag(fx, fy, fz) (x = w, y = h, z = d):
+ *   theta[i][j] = A[i][j] size_j / size_i (i != j), theta[i][i] = A[i][i] (a pure flip is
+ *   exactly +-1), theta[i][3] = 2 t_i / size_i.
+ * theta: [b][3][4], intensity: [b][nmod][2] (gain, bias), nmod in [1, MMAD_AUG_MAX_MOD]. */
+#define MMAD_AUG_MAX_MOD 4
+typedef struct mmad_augment_cfg {
+  double flip_p[3];
+  double rot_max[3];                   /* radians, about the d, h, w axes */
+  double scale_lo, scale_hi;
+  double trans_max[3];                 /* voxels */
+  double gain_lo[MMAD_AUG_MAX_MOD], gain_hi[MMAD_AUG_MAX_MOD];
+  double bias_lo[MMAD_AUG_MAX_MOD], bias_hi[MMAD_AUG_MAX_MOD];
+  int32_t nmod, pad_;
+} mmad_augment_cfg;
+int mmad_augment_draw(int b, int d, int h, int w, const mmad_augment_cfg* cfg,
+                      const uint64_t* seed, double* theta, double* intensity, void* stream);
+/* out[b][d][h][w] = gain * trilinear(x; theta) + bias, F.grid_sample(mode='bilinear',
+ * align_corners=False) semantics; padding: outside voxels read as zero (ZEROS) or
+ * coordinates clamped to the volume (BORDER).  gain_bias (may be NULL: no gain / bias):
+ * sample n reads (gain, bias) at gain_bias[n * gb_stride + {0, 1}].  A sample whose theta
+ * is exactly diag(+-1, +-1, +-1) with zero translation is an index-mirroring copy,
+ * bit-exact before gain and bias.  out must not alias x; d * h * w < 2^31. */
+enum { MMAD_PAD_ZEROS = 0, MMAD_PAD_BORDER = 1 };
+int mmad_affine_resample3d(int b, int d, int h, int w, const double* x, const double* theta,
+                           const double* gain_bias, int64_t gb_stride, int padding,
+                           double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -71,6 +71,20 @@ class WgradJob(C.Structure):
                                           "gx", "gy", "gz")])
 
 
+AUG_MAX_MOD = 4
+PAD_ZEROS, PAD_BORDER = 0, 1
+
+
+class AugmentCfg(C.Structure):
+    """mirror of mmad_augment_cfg (include/mmad.h); per-axis fields in tensor order d, h, w"""
+    _fields_ = ([("flip_p", C.c_double * 3), ("rot_max", C.c_double * 3),
+                 ("scale_lo", C.c_double), ("scale_hi", C.c_double),
+                 ("trans_max", C.c_double * 3)] +
+                [(n, C.c_double * AUG_MAX_MOD) for n in ("gain_lo", "gain_hi", "bias_lo",
+                                                         "bias_hi")] +
+                [("nmod", C.c_int32), ("pad_", C.c_int32)])
+
+
 _P = C.POINTER(ConvDesc)
 _PJ = C.POINTER(PackJob)
 _PD = C.POINTER(PackDual)
@@ -174,6 +188,10 @@ _SIGS = {
     "mmad_mean_std": (_i32, [_i32, _vp, _vp, _vp]),
     "mmad_bn_relu_bwd_reduce": (_i32, [_i32, _i64, _i32] + [_vp] * 8),
     "mmad_bn_relu_bwd_apply": (_i32, [_i32, _i64, _i32] + [_vp] * 9),
+    "mmad_augment_draw": (_i32, [_i32, _i32, _i32, _i32, C.POINTER(AugmentCfg), _vp, _vp, _vp,
+                                 _vp]),
+    "mmad_affine_resample3d": (_i32, [_i32, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _i32, _vp,
+                                      _vp]),
 }
 EXPORTS = tuple(_SIGS)
 

@@ -40,6 +40,7 @@ from . import tabular
 from . import layers as Lyr
 from . import medicalnet
 from .lightning_compat import (LightningModule, MulticlassF1Score, MulticlassMatthewsCorrCoef)
+from .augment import VolumeAugmenter
 from .preprocess import apply_batch_spec
 from .volume_ops import cast
 
@@ -110,6 +111,10 @@ class Base_Model(LightningModule, ABC):
             setattr(self, f"f1_score_{split}", MulticlassF1Score(num_classes=nc, average="macro"))
             setattr(self, f"f1_score_{split}_per_class",
                     MulticlassF1Score(num_classes=nc, average="none"))
+        # opt-in device augmentation (augment.VolumeAugmenter): a plain attribute, so models
+        # with and without the key have the same parameters, buffers and state-dict keys
+        cfg = self.hparams.get("augment")
+        self.augmenter = VolumeAugmenter(**cfg) if isinstance(cfg, dict) else None
 
     @abstractmethod
     def forward(self, *x):
@@ -126,6 +131,15 @@ class Base_Model(LightningModule, ABC):
         device, before any model math; every other batch passes through unchanged (the
         default dataset already normalised it on fetch, as the reference loader does)."""
         return apply_batch_spec(batch)
+
+    def augment_batch(self, batch, mode):
+        """hparams['augment'] (a dict of augment.AugmentConfig keys): random flip / affine /
+        intensity augmentation of the prepared batch on the device, in 'train' steps only.
+        Called by every ``general_step`` right after :meth:`prepare_batch` -- not from
+        ``on_after_batch_transfer``, which cannot see the mode (and would augment twice)."""
+        if self.augmenter is None or mode != "train":
+            return batch
+        return self.augmenter(batch)
 
     def on_after_batch_transfer(self, batch, dataloader_idx=0):
         """Lightning hook (runs after the batch reaches the device)."""
@@ -463,7 +477,7 @@ class Anat_CNN(Base_Model):
         return self.model(x)
 
     def general_step(self, batch, batch_idx, mode):
-        batch = self.prepare_batch(batch)
+        batch = self.augment_batch(self.prepare_batch(batch), mode)
         x = batch[self.batch_key].unsqueeze(1)   # raw f64 volume; conv 1 unfolds + casts it
         y = batch["label"]
         y_hat, loss = _logits_and_loss(self.criterion, self.forward(x), y)
@@ -601,7 +615,7 @@ class Anat_PET_CNN(Base_Model):
         return self.model_fuse(head_ops.concat_features(out_pet, out_mri))
 
     def general_step(self, batch, batch_idx, mode):
-        batch = self.prepare_batch(batch)
+        batch = self.augment_batch(self.prepare_batch(batch), mode)
         x_pet = batch["pet1451"].unsqueeze(1)
         x_mri = batch["mri"].unsqueeze(1)
         y = batch["label"]
@@ -670,7 +684,7 @@ class PET_MRI_EF(Base_Model):
         return self.model(x)
 
     def general_step(self, batch, batch_idx, mode):
-        batch = self.prepare_batch(batch)
+        batch = self.augment_batch(self.prepare_batch(batch), mode)
         from .volume_ops import StackedVolumes
         x = StackedVolumes([batch["pet1451"], batch["mri"]])
         y = batch["label"]
@@ -747,7 +761,7 @@ class PET_MRI_FMF(Base_Model):
         return self.fuse_model(fused)
 
     def general_step(self, batch, batch_idx, mode):
-        batch = self.prepare_batch(batch)
+        batch = self.augment_batch(self.prepare_batch(batch), mode)
         x_pet = batch["pet1451"].unsqueeze(1)      # raw f64; conv 1 unfolds + casts (:124-127)
         x_mri = batch["mri"].unsqueeze(1)
         y = batch["label"]
@@ -885,7 +899,7 @@ class Tri_ResNet_Tabular_Fusion(Base_Model):
         return self.model_fuse(head_ops.concat_features(out_pet, out_mri, out_tab))
 
     def general_step(self, batch, batch_idx, mode):
-        batch = self.prepare_batch(batch)
+        batch = self.augment_batch(self.prepare_batch(batch), mode)
         x_pet = batch["pet1451"].unsqueeze(1)
         x_mri = batch["mri"].unsqueeze(1)
         x_tab = cast(batch["tabular"].unsqueeze(1), torch.float32)
@@ -968,7 +982,7 @@ class Tabular_MRT_Model(_TabularStage2):
         return self.model_fuse(head_ops.concat_features(out_tabular, out_mri))
 
     def general_step(self, batch, batch_idx, mode):
-        batch = self.prepare_batch(batch)
+        batch = self.augment_batch(self.prepare_batch(batch), mode)
         x_mri = batch["mri"].unsqueeze(1)
         y = batch["label"]
         x_tab = cast(batch["tabular"].unsqueeze(1), torch.float32)
@@ -1015,7 +1029,7 @@ class PET_TABULAR_CNN(_TabularStage2):
         return self.model_fuse(head_ops.concat_features(out_pet, out_tab))
 
     def general_step(self, batch, batch_idx, mode):
-        batch = self.prepare_batch(batch)
+        batch = self.augment_batch(self.prepare_batch(batch), mode)
         x_pet = batch["pet1451"].unsqueeze(1)
         y = batch["label"]
         x_tab = cast(batch["tabular"].unsqueeze(1), torch.float32)
@@ -1079,7 +1093,7 @@ class All_Modalities_Fusion(Base_Model):
         return self.model_fuse(out)
 
     def general_step(self, batch, batch_idx, mode):
-        batch = self.prepare_batch(batch)
+        batch = self.augment_batch(self.prepare_batch(batch), mode)
         x_pet = batch["pet1451"].unsqueeze(1)
         x_mri = batch["mri"].unsqueeze(1)
         x_tab = cast(batch["tabular"].unsqueeze(1), torch.float32)

@@ -153,6 +153,15 @@ __device__ __forceinline__ double wave_sum_d(double v) {
   return v;
 }
 
+// splitmix64 finaliser: the counter-based hash behind every device-side random draw
+// (dropout masks, augmentation parameters)
+__device__ __forceinline__ uint64_t mix64(uint64_t z) {
+  z += 0x9E3779B97F4A7C15ull;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+
 static inline int hip_status(hipError_t e) { return e == hipSuccess ? MMAD_OK : MMAD_EHIP + (int)e; }
 static inline int launch_status() { return hip_status(hipGetLastError()); }
 static inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }

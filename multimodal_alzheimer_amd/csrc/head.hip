@@ -184,13 +184,6 @@ __global__ void cast_kernel(int64_t n, const TI* __restrict__ x, TO* __restrict_
   }
 }
 
-__device__ __forceinline__ uint64_t mix64(uint64_t z) {
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-
 template <typename T>
 __global__ void dropout_fwd_kernel(int64_t n, float p, uint64_t seed,
                                    const uint64_t* __restrict__ seed_dev, const T* __restrict__ x,
