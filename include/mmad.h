@@ -226,6 +226,22 @@ int mmad_wgrad_reduce_batch(int njobs, const mmad_wgrad_job* jobs, void* stream)
 int mmad_conv3d_wgrad_raw(const mmad_conv_desc* d, int in_dtype, const void* x, int dtype,
                           const void* dy, float* dw, float* dbias, void* workspace,
                           void* stream, void* reduce_stream);
+/* Input gradient of the MedicalNet stem (Cin 1 -> 64, 7^3, stride 2, pad 3) written straight
+ * into the dense raw volume (no reference counterpart; autograd's gradient w.r.t. the input
+ * of conv1, anat_cnn.py:29-31 -- what saliency / integrated-gradient maps differentiate):
+ * dy [n][do][ho][wo][64] NDHWC bf16 (as mmad_bnpool_bwd_apply writes it), w the fp32 torch
+ * weight [64][1][7][7][7] (rounded to bf16 as the forward's packing does), dx (n, 1, D, H, W)
+ * dense in out_dtype MMAD_F32 or MMAD_F64 (the raw input's dtype), fp32 accumulation in a
+ * fixed order: no atomics, two launches are bit-identical.  ws: mmad_stem_dgrad_ws_bytes
+ * bytes (the packed tap image, rebuilt by every call).  mmad_stem_dgrad_ok: 1 where the
+ * kernel applies (the stem geometry, any extents incl. odd ones, dtype MMAD_BF16); elsewhere
+ * mmad_conv3d_dgrad_raw returns MMAD_EUNSUPPORTED and the caller pads Ci to 8
+ * (mmad_pad_rows), runs mmad_conv3d_dgrad and extracts plane 0 (mmad_take_channel).
+ * dy, w, dx and ws are 16-byte aligned. */
+int mmad_stem_dgrad_ok(const mmad_conv_desc* d, int dtype, int out_dtype);
+int64_t mmad_stem_dgrad_ws_bytes(const mmad_conv_desc* d);
+int mmad_conv3d_dgrad_raw(const mmad_conv_desc* d, int dtype, const void* dy, const float* w,
+                          int out_dtype, void* dx, void* ws, void* stream);
 
 /* ---- BatchNorm3d / BatchNorm1d (+ fused ReLU and residual add) -------------------
  * Replaces nn.BatchNorm3d/1d + nn.ReLU + the residual `out += residual; relu`
@@ -419,6 +435,11 @@ int mmad_gather_channels(int in_dtype, int nsrc, const void* const* srcs,
                          int64_t batch_stride, int64_t vox_stride, int n, int64_t vox,
                          int cpad, int out_dtype, void* dst, void* stream);
 int mmad_pad_rows(int rows, int cin, int cout, const float* src, float* dst, void* stream);
+/* dst[r] = (out_dtype) src[r * cpad + ch]: one channel plane of an NDHWC volume (f32 / bf16)
+ * as a dense volume (f32 / f64) -- the inverse of mmad_gather_channels for one plane; the
+ * generic input gradient of a Cin = 1 conv takes plane 0 of its Ci-padded dgrad with it. */
+int mmad_take_channel(int in_dtype, int64_t rows, int cpad, int ch, const void* src,
+                      int out_dtype, void* dst, void* stream);
 int mmad_concat_channels(int dtype, int64_t rows, int ca, const void* a, int cb,
                          const void* b, void* dst, void* stream);
 int mmad_split_channels(int dtype, int64_t rows, int ca, int cb, const void* src, void* a,

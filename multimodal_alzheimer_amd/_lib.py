@@ -121,6 +121,9 @@ _SIGS = {
     "mmad_stem_raw_ok": (_i32, [_P, _i32, _i32]),
     "mmad_conv3d_fwd_raw": (_i32, [_P, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "mmad_conv3d_wgrad_raw": (_i32, [_P, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mmad_stem_dgrad_ok": (_i32, [_P, _i32, _i32]),
+    "mmad_stem_dgrad_ws_bytes": (_i64, [_P]),
+    "mmad_conv3d_dgrad_raw": (_i32, [_P, _i32, _vp, _vp, _i32, _vp, _vp, _vp]),
     "mmad_bn_stats_parts": (_i64, [_i64, _i32]),
     "mmad_bn_stats": (_i32, [_i32, _i64, _i32, _vp, _vp, _vp]),
     "mmad_bn_parts_fold": (_i32, [_i32, _i32, _vp, _i32, _vp, _vp]),
@@ -180,6 +183,7 @@ _SIGS = {
     "mmad_gather_channels": (_i32, [_i32, _i32, _vp, _i64, _i64, _i32, _i64, _i32, _i32, _vp,
                                     _vp]),
     "mmad_pad_rows": (_i32, [_i32, _i32, _i32, _vp, _vp, _vp]),
+    "mmad_take_channel": (_i32, [_i32, _i64, _i32, _i32, _vp, _i32, _vp, _vp]),
     "mmad_concat_channels": (_i32, [_i32, _i64, _i32, _vp, _i32, _vp, _vp, _vp]),
     "mmad_split_channels": (_i32, [_i32, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
     "mmad_max2_fwd": (_i32, [_i32, _i64, _vp, _vp, _vp, _vp, _vp]),

@@ -155,6 +155,17 @@ __global__ __launch_bounds__(256) void split_ch_kernel(int64_t rows, int ca, int
   }
 }
 
+// dst[r] = src[r * cpad + ch]: one channel plane of an NDHWC volume as a dense volume (the
+// inverse of gather_channels_kernel for one plane)
+template <typename TI, typename TO>
+__global__ __launch_bounds__(256) void take_channel_kernel(int64_t rows, int cpad, int ch,
+                                                           const TI* __restrict__ src,
+                                                           TO* __restrict__ dst) {
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < rows;
+       i += (int64_t)gridDim.x * blockDim.x)
+    dst[i] = (TO)load_as_f32(src, i * cpad + ch);
+}
+
 bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 }  // namespace
@@ -194,6 +205,25 @@ int mmad_pad_rows(int rows, int cin, int cout, const float* src, float* dst, voi
   if (!src || !dst) return MMAD_ENULL;
   hipLaunchKernelGGL(pad_rows_kernel, dim3(grid_of((int64_t)rows * cout)), dim3(256), 0,
                      as_stream(stream), rows, cin, cout, src, dst);
+  return launch_status();
+}
+
+int mmad_take_channel(int in_dtype, int64_t rows, int cpad, int ch, const void* src,
+                      int out_dtype, void* dst, void* stream) {
+  if (rows <= 0 || cpad <= 0 || ch < 0 || ch >= cpad) return MMAD_EBADSHAPE;
+  if (!src || !dst) return MMAD_ENULL;
+  if (!aligned16(src) || !aligned16(dst)) return MMAD_EBADSHAPE;
+  hipStream_t st = as_stream(stream);
+  const unsigned grid = grid_of(rows);
+#define TAKE(TI, TO)                                                                       \
+  hipLaunchKernelGGL((take_channel_kernel<TI, TO>), dim3(grid), dim3(256), 0, st, rows, cpad, \
+                     ch, (const TI*)src, (TO*)dst)
+  if (in_dtype == MMAD_BF16 && out_dtype == MMAD_F32) TAKE(u16, float);
+  else if (in_dtype == MMAD_BF16 && out_dtype == MMAD_F64) TAKE(u16, double);
+  else if (in_dtype == MMAD_F32 && out_dtype == MMAD_F32) TAKE(float, float);
+  else if (in_dtype == MMAD_F32 && out_dtype == MMAD_F64) TAKE(float, double);
+  else return MMAD_EBADDTYPE;
+#undef TAKE
   return launch_status();
 }
 

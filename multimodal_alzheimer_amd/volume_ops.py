@@ -180,6 +180,9 @@ REDUCE_STREAM = os.environ.get("MMAD_REDUCE_STREAM", "0") == "1"
 # MMAD_STEM_RAW=0: the Cin-1 stem reads the W-unfolded copy written by
 # mmad_conv_unfold_input instead of the raw volume (A/B switch; mmad_conv3d_fwd_raw)
 STEM_RAW = os.environ.get("MMAD_STEM_RAW", "1") != "0"
+# MMAD_STEM_DGRAD=0: the stem's input gradient takes the generic Ci-padded route instead of
+# the dedicated kernel (A/B switch; raw_input_grad)
+STEM_DGRAD = os.environ.get("MMAD_STEM_DGRAD", "1") != "0"
 _SIDE = {}
 _JOIN_PENDING = set()
 
@@ -377,7 +380,10 @@ class StackedVolumes:
             self.ptrs = [x.data_ptr() + ch * s[1] * es for ch in range(c)]
             self.bstride, self.vstride = s[0], s[4]
             self._keep = [x]
+            self.requires_grad = torch.is_grad_enabled() and srcs.requires_grad
         else:
+            # a source that asks for a gradient cannot get one (the first conv raises)
+            self.requires_grad = torch.is_grad_enabled() and any(t.requires_grad for t in srcs)
             srcs = [t.contiguous() for t in srcs]
             x = srcs[0]
             if any(t.shape != x.shape or t.dtype != x.dtype or t.device != x.device
@@ -414,6 +420,45 @@ def _pad_rows(src, rows, cin, cout, shape):
     return dst
 
 
+def raw_input_grad(d, gy, weight, out_dtype, route=None):
+    """dX of a Cin = 1 conv as a dense (N, 1, D, H, W) volume in ``out_dtype`` (float32 or
+    float64, the raw input's dtype); ``gy`` is the NDHWC output gradient in the compute dtype.
+
+    ``route``: "stem" = the dedicated MFMA kernel (mmad_conv3d_dgrad_raw: the MedicalNet stem
+    in bf16), "generic" = weight Ci padded to 8 + mmad_conv3d_dgrad + plane 0 extracted
+    (mmad_take_channel; every other Cin = 1 conv and fp32 compute); None picks "stem" where
+    mmad_stem_dgrad_ok says it applies."""
+    lib = L.load()
+    cdtype = gy.dtype
+    dt, odt = L.dtype_code(cdtype), L.dtype_code(out_dtype)
+    if route is None:
+        route = "stem" if STEM_DGRAD and lib.mmad_stem_dgrad_ok(d, dt, odt) == 1 else "generic"
+    w = weight.detach().contiguous()
+    dx = torch.empty((d.n, 1, d.di, d.hi, d.wi), dtype=out_dtype, device=gy.device)
+    if route == "stem":
+        ws = torch.empty(lib.mmad_stem_dgrad_ws_bytes(d), dtype=torch.uint8, device=gy.device)
+        L.call("mmad_conv3d_dgrad_raw", d, dt, L.ptr(gy), L.ptr(w), odt, L.ptr(dx), L.ptr(ws),
+               L.stream())
+        return dx
+    taps = d.kd * d.kh * d.kw
+    d8 = L.ConvDesc(*_desc_tuple(d))
+    d8.ci = 8
+    geo = (f"Cin 1 -> {d.co}, kernel {(d.kd, d.kh, d.kw)}, stride {(d.sd, d.sh, d.sw)}, "
+           f"padding {(d.pd, d.ph, d.pw)}, input {(d.di, d.hi, d.wi)}, {cdtype}")
+    if lib.mmad_conv_packed_elems(d8, dt, 1) < 0:
+        raise L.MMADError(f"conv3d: no input-gradient kernel for this raw-input conv ({geo})")
+    w8 = _pad_rows(w, d.co, taps, 8 * taps, (d.co, 8, d.kd, d.kh, d.kw))
+    wpt = pack_weight(d8, dt, w8, cdtype, True)
+    dx8 = _empty_vol(d.n, 8, d.di, d.hi, d.wi, cdtype, gy.device)
+    rc = lib.mmad_conv3d_dgrad(d8, dt, L.ptr(gy), L.ptr(wpt), L.ptr(dx8), L.stream())
+    if rc == L.EUNSUPPORTED:
+        raise L.MMADError(f"conv3d: no input-gradient kernel for this raw-input conv ({geo})")
+    L.check(rc, "mmad_conv3d_dgrad")
+    L.call("mmad_take_channel", dt, d.n * d.di * d.hi * d.wi, 8, 0, L.ptr(dx8), odt, L.ptr(dx),
+           L.stream())
+    return dx
+
+
 class _Conv3dFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, geom, cdtype, want_stats, packed=None):
@@ -430,9 +475,9 @@ class _Conv3dFn(torch.autograd.Function):
         if isinstance(x, StackedVolumes) or (d.ci > 1 and d.ci % 8):
             # Cin in 2..7 (early fusion): channel-padded operand and weight (fusion.hip);
             # the zero lanes contribute exact zeros
-            if ctx.needs_input_grad[0]:
-                raise L.MMADError("conv3d: gradient w.r.t. a channel-stacked raw input is "
-                                  "not supported (the input never needs one)")
+            if ctx.needs_input_grad[0] or (isinstance(x, StackedVolumes) and x.requires_grad):
+                raise L.MMADError("conv3d: input gradients for channel-stacked raw inputs "
+                                  "(early fusion, Cin 2..7) are not implemented yet")
             sv = x if isinstance(x, StackedVolumes) else StackedVolumes(x)
             if sv.shape[1] == 1:
                 raise L.MMADError("a single raw volume goes to conv3d as a (B,1,D,H,W) tensor")
@@ -443,9 +488,9 @@ class _Conv3dFn(torch.autograd.Function):
             d.ci = 8
             packed = None
         elif d.ci == 1:
-            if ctx.needs_input_grad[0]:
-                raise L.MMADError("conv3d: gradient w.r.t. a 1-channel raw input volume "
-                                  "is not supported (the input never needs one)")
+            if ctx.needs_input_grad[0] and x.dtype not in (torch.float32, torch.float64):
+                raise L.MMADError("conv3d: the gradient w.r.t. a raw input volume is written "
+                                  f"in float32 or float64, not {x.dtype}")
             xc = x.contiguous()
             in_dt = L.dtype_code(xc.dtype)
             if STEM_RAW and lib.mmad_stem_raw_ok(d, in_dt, dt) == 1:
@@ -493,6 +538,7 @@ class _Conv3dFn(torch.autograd.Function):
         ctx.cdtype = cdtype
         ctx.has_bias = bias is not None
         ctx.xshape = tuple(x.shape)
+        ctx.xdtype = x.dtype
         if want_stats:
             ctx.mark_non_differentiable(stats)
             return y, stats
@@ -510,7 +556,10 @@ class _Conv3dFn(torch.autograd.Function):
         if gy.dtype != cdtype:
             gy = cast(gy, cdtype)
         dx = dw = db = None
-        if ctx.needs_input_grad[0]:
+        if ctx.needs_input_grad[0] and d.ci == 1:
+            # a raw (B, 1, D, H, W) volume asked for its gradient (explain.py)
+            dx = raw_input_grad(d, gy, weight, ctx.xdtype)
+        elif ctx.needs_input_grad[0]:
             wpt = ctx.wpt if ctx.wpt is not None else pack_weight(d, dt, weight, cdtype, True)
             dx = _empty_vol(d.n, d.ci, d.di, d.hi, d.wi, cdtype, gy.device)
             if ctx.bnsum is not None:
