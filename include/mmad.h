@@ -39,7 +39,8 @@ extern "C" {
 enum { MMAD_OK = 0, MMAD_EBADSHAPE = 1001, MMAD_EBADDTYPE = 1002, MMAD_ENULL = 1003,
        MMAD_EUNSUPPORTED = 1004, MMAD_EHIP = 2000 };
 
-enum { MMAD_F32 = 0, MMAD_BF16 = 1, MMAD_F64 = 2 };
+/* MMAD_F16 and MMAD_BITS (1 bit per voxel) are storage kinds of the dataset cache only */
+enum { MMAD_F32 = 0, MMAD_BF16 = 1, MMAD_F64 = 2, MMAD_F16 = 3, MMAD_BITS = 4 };
 
 /* One 3D convolution (torch.nn.Conv3d semantics, groups = 1).  `do_` is the output
  * depth (`do` is a C keyword). */
@@ -546,6 +547,51 @@ enum { MMAD_PAD_ZEROS = 0, MMAD_PAD_BORDER = 1 };
 int mmad_affine_resample3d(int b, int d, int h, int w, const double* x, const double* theta,
                            const double* gain_bias, int64_t gb_stride, int padding,
                            double* out, void* stream);
+
+/* ---- device-resident dataset cache (float64 in and out, compact exact storage) --------
+ * Replaces the DataLoader's collate + .to(device) per batch and nibabel's get_fdata
+ * widening on the loader workers (pkg/utils/dataloader.py:197-211): the sample table's
+ * volumes are narrowed into HBM once, and every batch is assembled on the device from an
+ * index that the kernel reads when it runs (so a captured launch fetches its own next batch).
+ *
+ * A store holds `capacity` slots of one scan each; slot s starts at byte
+ * s * mmad_cache_stride_bytes(kind, vox), the scan's bytes rounded up to 16 (kind: MMAD_F64,
+ * MMAD_F32, MMAD_F16, or MMAD_BITS = ceil(vox / 8) bytes, voxel v = bit v % 8 of byte v / 8).
+ * The store is 16-byte aligned; vox < 2^31.  ws: mmad_cache_ws_bytes() bytes, 8-byte aligned,
+ * free for reuse once the call's kernels have run.
+ *
+ * mmad_cache_store: src [n][vox] float64 -> slots slot0 .. slot0 + n - 1 in `kind` (float16
+ *   narrows through float32, as torch's .half()); *mismatches += the number of voxels whose
+ *   widened stored value differs from the source in any bit (0 for an exact store).
+ * mmad_cache_pack_mask: the same for MMAD_BITS (bit = the voxel is exactly 1.0);
+ *   *nonbinary += the number of voxels that are neither +0.0 nor 1.0.
+ * Both count in two fixed stages (per block into ws, then one block); the addition to the
+ * caller's counter is the only atomic, and nothing else depends on it.                  */
+int64_t mmad_cache_stride_bytes(int kind, int64_t vox);     /* -1: unknown kind / vox <= 0 */
+int64_t mmad_cache_ws_bytes(void);
+int mmad_cache_store(int kind, int n, int64_t vox, const double* src, void* store, int64_t slot0,
+                     int64_t capacity, uint64_t* mismatches, void* ws, void* stream);
+int mmad_cache_pack_mask(int n, int64_t vox, const double* src, void* store, int64_t slot0,
+                         int64_t capacity, uint64_t* nonbinary, void* ws, void* stream);
+/* mmad_cache_fetch: out [b][dout][hout][wout] float64 (contiguous, 8-byte aligned); entry k
+ *   holds scan i = order[*cursor + k] (cursor NULL: 0) of a store of n scans (di, hi, wi),
+ *   widened exactly (bits: 0.0 / 1.0) and placed by the centre rule: per axis
+ *   offset = floor((out - in) / 2), negative crops, positive zero-fills.  order (device,
+ *   order_len entries) and cursor (device scalar) are read when the kernel runs.  A position
+ *   outside [0, order_len) or an index outside [0, n) is never dereferenced: that entry is
+ *   zeros and *bad (device int32, sticky) is set to 1.  Unchanged geometry is a flat copy in
+ *   16-byte vectors both ways (8-byte stores for an entry that starts 8 bytes off 16, which an
+ *   odd vox gives every other entry); otherwise one wave per output row, 16-byte stores along
+ *   W, each store's two source voxels loaded as one vector where the source index is even,
+ *   row heads and tails per element.
+ * mmad_cache_fetch_rows: the same gather for labels [n] int64 and tabular rows [n][cols]
+ *   float64 in one launch (either output may be NULL).                                  */
+int mmad_cache_fetch(int kind, int b, int64_t n, int di, int hi, int wi, int dout, int hout,
+                     int wout, const void* store, const int64_t* order, const int64_t* cursor,
+                     int64_t order_len, double* out, int32_t* bad, void* stream);
+int mmad_cache_fetch_rows(int b, int64_t n, int cols, const int64_t* labels, const double* tab,
+                          const int64_t* order, const int64_t* cursor, int64_t order_len,
+                          int64_t* out_labels, double* out_tab, int32_t* bad, void* stream);
 
 #ifdef __cplusplus
 }

@@ -5,8 +5,8 @@ weighted-CE loss, as hand-written HIP kernels behind the C ABI in include/mmad.h
 (libmmad_hip.so), exposed through drop-in replacements of the reference's ``pkg.models``
 LightningModule classes (see classifiers.py) and the MedicalNet API (medicalnet.py).
 """
-from . import (_lib, augment, explain, head_ops, layers, medicalnet, preprocess,  # noqa: F401
-               tabular, volume_ops)
+from . import (_lib, augment, device_cache, explain, head_ops, layers, medicalnet,  # noqa: F401
+               preprocess, tabular, volume_ops)
 from .classifiers import (All_Modalities_Fusion, Anat_CNN, Anat_PET_CNN, Base_Model,  # noqa
                           FocalLoss, PET_CNN_ResNet, PET_MRI_EF, PET_MRI_FMF,
                           PET_MRI_ResNet_Fusion, PET_TABULAR_CNN,

@@ -17,6 +17,7 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MMAD_LIB_PATH") or os.path.join(_PKG, "libmmad_hip.so")
 
 F32, BF16, F64 = 0, 1, 2
+F16, BITS = 3, 4                  # storage kinds of the dataset cache only (device_cache)
 EUNSUPPORTED = 1004
 EHIP = 2000
 _HIP_OOM = 2   # hipErrorOutOfMemory
@@ -196,6 +197,14 @@ _SIGS = {
                                  _vp]),
     "mmad_affine_resample3d": (_i32, [_i32, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _i32, _vp,
                                       _vp]),
+    "mmad_cache_stride_bytes": (_i64, [_i32, _i64]),
+    "mmad_cache_ws_bytes": (_i64, []),
+    "mmad_cache_store": (_i32, [_i32, _i32, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp]),
+    "mmad_cache_pack_mask": (_i32, [_i32, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp]),
+    "mmad_cache_fetch": (_i32, [_i32, _i32, _i64] + [_i32] * 6 + [_vp, _vp, _vp, _i64, _vp, _vp,
+                                                                 _vp]),
+    "mmad_cache_fetch_rows": (_i32, [_i32, _i64, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp,
+                                     _vp]),
 }
 EXPORTS = tuple(_SIGS)
 

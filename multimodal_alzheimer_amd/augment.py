@@ -26,8 +26,9 @@ model's ``general_step`` apply one in ``'train'`` mode).  There is no CPU path a
 the inputs are data.
 
 Out of scope: per-voxel noise (Box-Muller per voxel would make the resample VALU-bound),
-gamma, elastic deformation, nearest-neighbour interpolation, and a device-resident dataset
-cache.
+gamma, elastic deformation and nearest-neighbour interpolation.  The batch can come from a
+device-resident dataset cache (device_cache.DeviceVolumeCache), whose fetched batch dict the
+augmenter takes unchanged.
 """
 import math
 

@@ -46,6 +46,14 @@ depends on it:
   ``volume_ops._BN_UPDATES`` so the next evaluation refolds;
 * dropout draws its seed on the device (``head_ops.dropout``), so every replay gets a
   fresh mask.
+
+``feed=`` (a device_cache.CacheFeed) puts the input pipeline into the graph as well: the
+captured body begins with ``feed.fetch_into(self.static)`` -- the fetch kernels read the
+epoch's order at a device cursor, then the cursor moves on -- so ``step()`` with no batch
+replays a step that loads its own next batch, with no host work and no copy; the feed, which
+counts steps on the host, uploads the next epoch's order between replays.  Under
+``collectives="staged"`` the fetch belongs to the first graph.  The eager warm-up steps run on
+``batch`` (default: the feed's first batch, which the first replay then trains on again).
 """
 import os
 
@@ -179,13 +187,21 @@ class StagedBackward:
 
 
 class GraphedTrainStep:
-    def __init__(self, model, optimizer, batch, warmup=3, reducer=None, collectives="inside",
-                 cuts=DEFAULT_CUTS):
+    def __init__(self, model, optimizer, batch=None, warmup=3, reducer=None,
+                 collectives="inside", cuts=DEFAULT_CUTS, feed=None):
         """``reducer``: a data_parallel.GradAllReduce (for ``collectives="staged"`` built
         with ``stages=backward_stages(model, cuts)[1]``).  ``collectives``: see the module
-        docstring."""
+        docstring.  ``feed``: a device_cache.CacheFeed whose fetch opens the captured step
+        (``batch`` may then be None)."""
         self.model, self.optimizer = model, optimizer
         self.reducer = reducer
+        self.feed = feed
+        if feed is not None:
+            feed.prepare()                   # device state + first kernel launches, pre-capture
+            if batch is None:
+                batch = feed.peek()
+        elif batch is None:
+            raise ValueError("GraphedTrainStep needs a batch (or a feed)")
         if reducer is not None and collectives not in COLLECTIVES:
             raise ValueError(f"collectives must be one of {COLLECTIVES}, not {collectives!r}")
         self.mode = collectives if reducer is not None else None
@@ -272,7 +288,7 @@ class GraphedTrainStep:
                 if self.mode == "after":
                     g = torch.cuda.CUDAGraph()
                     with torch.cuda.graph(g, capture_error_mode=_CAPTURE_MODE):
-                        self.out = model.general_step(self.static, 0, "train")
+                        self.out = model.general_step(self._fetched(), 0, "train")
                         self.out["loss"].backward(self._one)
                         volume_ops.flush_wgrad_reduce()
                     self.graphs.append(g)
@@ -281,7 +297,7 @@ class GraphedTrainStep:
                     try:
                         g = torch.cuda.CUDAGraph()
                         with torch.cuda.graph(g, capture_error_mode=_CAPTURE_MODE):
-                            self.out = model.general_step(self.static, 0, "train")
+                            self.out = model.general_step(self._fetched(), 0, "train")
                             staged.run(0, self.out["loss"], self._one)
                     finally:
                         staged.disarm()
@@ -303,13 +319,19 @@ class GraphedTrainStep:
         else:
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g, capture_error_mode=_CAPTURE_MODE):
-                self.out = model.general_step(self.static, 0, "train")
+                self.out = model.general_step(self._fetched(), 0, "train")
                 self.out["loss"].backward(self._one)
                 volume_ops.flush_wgrad_reduce()
                 if reducer is not None:
                     reducer.finish()
                 self._opt_step()
             self.graphs.append(g)
+
+    def _fetched(self):
+        """the step's input buffers; with a feed, filled by its (captured) fetch first"""
+        if self.feed is not None:
+            self.feed.fetch_into(self.static)
+        return self.static
 
     def _eager(self):
         self.optimizer.zero_grad(set_to_none=True)
@@ -322,8 +344,13 @@ class GraphedTrainStep:
 
     def __call__(self, batch=None):
         """Replay one step; ``batch`` (same keys / shapes) is copied into the graph's input
-        buffers first.  Returns the step's {'loss', 'outputs', 'labels'} (graph-owned
-        tensors, overwritten by the next replay)."""
+        buffers first.  With a feed the step fetches its own batch and takes none.  Returns
+        the step's {'loss', 'outputs', 'labels'} (graph-owned tensors, overwritten by the next
+        replay)."""
+        if self.feed is not None:
+            if batch is not None:
+                raise ValueError("this step is fed by its CacheFeed: call it without a batch")
+            self.feed.before_replay()        # host step count; next epoch's order when due
         if batch is not None:
             for k, v in batch.items():
                 if torch.is_tensor(v):
