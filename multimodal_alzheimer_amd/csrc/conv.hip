@@ -32,6 +32,8 @@
 //  * XCD-aware tile order: each XCD walks a contiguous range of (m, n) tiles, n fastest;
 //  * epilogue: bias, BN partial sums (sum, sum of squares per channel) from the fp32
 //    accumulators, bf16 tile transposed through LDS into 16-byte channel-vector stores.
+#include <cstring>
+
 #include "common.h"
 #include "reduce.h"
 #include "patchconv.h"
@@ -1300,35 +1302,14 @@ bool geom_ok(const Geom& g, int dtype) {
          src_vox < (int64_t(1) << 31) && dst_vox < (int64_t(1) << 31);   // 32-bit voxel ids
 }
 
-// the patch-resident kernel (patchconv.hip) for narrow stride-1 bf16 convs
+// the geometry record of the patch / residue-class / sub-patch kernels (patchconv.h), with
+// the residual / ReLU epilogue of g
 mmad_patch::Geo patch_geo(const Geom& g) {
-  return mmad_patch::Geo{g.nb, g.Cs, g.Nd, g.Kpad, g.Ds, g.Hs, g.Ws, g.Dd, g.Hd, g.Wd,
-                         g.KD, g.KH, g.KW, g.pd, g.ph, g.pw, g.dd, g.dh, g.dw};
-}
-bool use_patch(const Geom& g, int dtype) {
-  return dtype == MMAD_BF16 && g.sd == 1 && g.sh == 1 && g.sw == 1 &&
-         mmad_patch::ok(patch_geo(g));
-}
-// the residue-class kernel (latticeconv.hip) for dilated stride-1 bf16 convs on 4d^3 grids
-bool use_lattice(const Geom& g, int dtype) {
-  return dtype == MMAD_BF16 && g.sd == 1 && g.sh == 1 && g.sw == 1 &&
-         mmad_lattice::ok(patch_geo(g));
-}
-bool use_lattice8(const Geom& g, int dtype) {
-  return dtype == MMAD_BF16 && g.sd == 1 && g.sh == 1 && g.sw == 1 &&
-         mmad_lattice8::ok(patch_geo(g));
-}
-bool use_pwgrad(const Geom& g, int dtype) {
-  return dtype == MMAD_BF16 && g.sd == 1 && g.sh == 1 && g.sw == 1 &&
-         mmad_pwgrad::ok(patch_geo(g));
-}
-// the parity-sub-patch kernel (s2conv.hip) for the stride-2 3^3 forward (layer2.0.conv1)
-bool use_s2(const Geom& g, int dtype) {
-  return dtype == MMAD_BF16 && mmad_s2::ok(patch_geo(g), g.sd, g.sh, g.sw);
-}
-bool use_lattice_wgrad(const Geom& g, int dtype) {
-  return dtype == MMAD_BF16 && g.sd == 1 && g.sh == 1 && g.sw == 1 &&
-         mmad_lattice::wgrad_ok(patch_geo(g));
+  mmad_patch::Geo q{g.nb, g.Cs, g.Nd, g.Kpad, g.Ds, g.Hs, g.Ws, g.Dd, g.Hd, g.Wd,
+                    g.KD, g.KH, g.KW, g.pd, g.ph, g.pw, g.dd, g.dh, g.dw};
+  q.res = g.res;
+  q.relu = g.relu;
+  return q;
 }
 
 int bn_of(const Geom& g) { return g.Nd <= 64 ? 64 : 128; }
@@ -1576,10 +1557,105 @@ unsigned grid_for(int64_t total, int block = 256) {
   return (unsigned)std::max<int64_t>(1, std::min<int64_t>(cdiv(total, block), 65536));
 }
 
+// ---- the forward route ---------------------------------------------------------------------
+// Which kernel runs a forward-shaped conv (a forward, or a stride-1 input gradient run as
+// one) is decided here and nowhere else: every entry point resolves, then launch_route()
+// switches on the leaf.  The leaves, in precedence order:
+enum Leaf { STEM, LATTICE5, LATTICE_ZP, LATTICE, LATTICE8, PATCHZ, PATCH, S2, PW, IGEMM, NONE };
+// what the caller needs beyond bias + BN statistics, and which leaves have it:
+//   EPI_RES    residual / ReLU (mmad_conv3d_fwd_ex): every leaf but STEM and PW
+//   EPI_BNSUM  BN-backward partial sums (mmad_conv3d_dgrad_bnsum): LATTICE_ZP, LATTICE8, PATCH
+enum Epi { EPI_NONE, EPI_RES, EPI_BNSUM };
+bool leaf_has(Leaf l, Epi e) {
+  if (e == EPI_RES) return l != STEM && l != PW;
+  if (e == EPI_BNSUM) return l == LATTICE_ZP || l == LATTICE8 || l == PATCH;
+  return true;
+}
+// tiles: M tiles of the launch = rows of the BN partial buffer it writes (-1 with NONE)
+struct Route { Leaf leaf; int64_t tiles; };
+
+// d: the conv whose forward this is (nullptr for a dgrad run as a forward: no stem or
+// pointwise leaf); g: its forward-shaped geometry.  A residual / ReLU request passes over the
+// pointwise GEMM and is refused on the unfolded stem layout; a BN-sum request is refused
+// (NONE) unless the kernel that would run the conv has that epilogue -- never handed to one
+// that ignores it.  launch = false (a row query) leaves out the launch-time geom_ok refusal.
+Route resolve(const mmad_conv_desc* d, const Geom& g, int dtype, Epi epi, bool launch = true) {
+  const Route none{NONE, -1};
+  auto pick = [&](Leaf l, int64_t tiles) { return leaf_has(l, epi) ? Route{l, tiles} : none; };
+  const bool u = d != nullptr && unfolded(d);
+  if (u && epi != EPI_NONE) return none;        // the stem keeps its own epilogue
+  if (u && mmad_stem::fwd_ok(d, dtype) && stem_kernel_on())
+    return pick(STEM, mmad_stem::fwd_stats_rows(d));
+  if (launch && !geom_ok(g, dtype)) return none;
+  if (!u && dtype == MMAD_BF16) {
+    const mmad_patch::Geo q = patch_geo(g);
+    if (g.sd == 1 && g.sh == 1 && g.sw == 1) {
+      if (mmad_lattice5::ok(q)) return pick(LATTICE5, mmad_lattice5::tiles(q));
+      // 4d^3 and ragged grids: the plane-pair form where it applies (its tiles then count
+      // toward the residue-class fill rule), else the one-plane kernel
+      const bool zp = mmad_lattice_zp::ok(q);
+      const int64_t lt = zp ? mmad_lattice_zp::tiles(q) : mmad_lattice::tiles(q);
+      if (mmad_lattice::ok(q, lt)) return pick(zp ? LATTICE_ZP : LATTICE, lt);
+      if (mmad_lattice8::ok(q)) return pick(LATTICE8, mmad_lattice8::tiles(q));
+      if (mmad_patch::ok(q))
+        return mmad_patchz::ok(q) ? pick(PATCHZ, mmad_patchz::tiles(q))
+                                  : pick(PATCH, mmad_patch::tiles(q));
+    }
+    if (mmad_s2::ok(q, g.sd, g.sh, g.sw)) return pick(S2, mmad_s2::tiles(q));
+  }
+  if (d != nullptr && leaf_has(PW, epi) && mmad_pw::fwd_ok(d, dtype))
+    return pick(PW, mmad_pw::fwd_tiles(d));
+  return pick(IGEMM, cdiv(g.M, fwd_tile_rows(g, dtype)));
+}
+
+// q: patch_geo(g) plus whatever epilogue fields the caller set
+int launch_route(const Route& r, const mmad_conv_desc* d, const Geom& g, int dtype,
+                 const mmad_patch::Geo& q, const void* x, const void* wp, const float* bias,
+                 void* y, float* stats, void* stream) {
+  switch (r.leaf) {
+    case STEM: return mmad_stem::fwd(d, x, wp, bias, y, stats, stream);
+    case LATTICE5: return mmad_lattice5::fwd(q, x, wp, bias, y, stats, stream);
+    case LATTICE_ZP: return mmad_lattice_zp::fwd(q, x, wp, bias, y, stats, stream);
+    case LATTICE: return mmad_lattice::fwd(q, x, wp, bias, y, stats, stream);
+    case LATTICE8: return mmad_lattice8::fwd(q, x, wp, bias, y, stats, stream);
+    case PATCHZ: return mmad_patchz::fwd(q, x, wp, bias, y, stats, stream);
+    case PATCH: return mmad_patch::fwd(q, x, wp, bias, y, stats, stream);
+    case S2: return mmad_s2::fwd(q, g.sd, g.sh, g.sw, x, wp, bias, y, stats, stream);
+    case PW: return mmad_pw::fwd(d, x, wp, bias, y, stats, stream);
+    case IGEMM: return run_igemm<FWD>(g, dtype, g.M, 1, x, wp, bias, y, stats, as_stream(stream));
+    case NONE: break;
+  }
+  return MMAD_EUNSUPPORTED;
+}
+
+// the stride-1 input gradient as a forward conv over dY (dgrad_as_fwd): its geometry in *gf
+// and its route; NONE also where the pointwise dgrad GEMM or a strided path has the conv
+Route dgrad_fwd_route(const mmad_conv_desc* d, int dtype, Epi epi, Geom* gf) {
+  if (!desc_ok(d) || (dtype != MMAD_F32 && dtype != MMAD_BF16) || unfolded(d) ||
+      mmad_pw::ok(d, dtype) || !dgrad_as_fwd(d))
+    return Route{NONE, -1};
+  *gf = dgrad_fwd_geom(d, dtype);
+  return resolve(nullptr, *gf, dtype, epi);
+}
+
 }  // namespace
 
 // =====================================================================================
 extern "C" {
+
+// the run-time overrides of the switches the routes above (and the pooling / pointwise
+// kernels) read; returns the previous mode, -1 for an unknown name
+int mmad_set_kernel_variant(const char* name, int value) {
+  if (name == nullptr) return -1;
+  if (std::strcmp(name, "lattice_zp") == 0) return mmad_lattice_zp::set_mode(value);
+  if (std::strcmp(name, "lattice") == 0) return mmad_lattice::set_mode(value);
+  if (std::strcmp(name, "lattice8") == 0) return mmad_lattice8::set_mode(value);
+  if (std::strcmp(name, "lattice5") == 0) return mmad_lattice5::set_mode(value);
+  if (std::strcmp(name, "pool_run") == 0) return mmad_pool::set_run_mode(value);
+  if (std::strcmp(name, "patchz") == 0) return mmad_patchz::set_mode(value);
+  if (std::strcmp(name, "pw_wg3_dedup") == 0) return mmad_pw::set_wg3_dedup(value);
+  return -1;
+}
 
 int64_t mmad_conv_packed_elems(const mmad_conv_desc* d, int dtype, int for_dgrad) {
   if (!desc_ok(d)) return -1;
@@ -1762,15 +1838,7 @@ int mmad_conv_unfold_input(const mmad_conv_desc* d, int in_dtype, const void* x,
 
 int64_t mmad_conv3d_stats_rows(const mmad_conv_desc* d, int dtype) {
   if (!desc_ok(d)) return -1;
-  if (unfolded(d) && mmad_stem::fwd_ok(d, dtype) && stem_kernel_on())
-    return mmad_stem::fwd_stats_rows(d);
-  const Geom g = fwd_geom(d, dtype);
-  if (!unfolded(d) && use_lattice(g, dtype)) return mmad_lattice::tiles(patch_geo(g));
-  if (!unfolded(d) && use_lattice8(g, dtype)) return mmad_lattice8::tiles(patch_geo(g));
-  if (!unfolded(d) && use_patch(g, dtype)) return mmad_patch::tiles(patch_geo(g));
-  if (!unfolded(d) && use_s2(g, dtype)) return mmad_s2::tiles(patch_geo(g));
-  if (mmad_pw::fwd_ok(d, dtype)) return mmad_pw::fwd_tiles(d);
-  return cdiv(g.M, fwd_tile_rows(g, dtype));
+  return resolve(d, fwd_geom(d, dtype), dtype, EPI_NONE, false).tiles;
 }
 
 int mmad_conv3d_fwd(const mmad_conv_desc* d, int dtype, const void* x, const void* wp,
@@ -1779,20 +1847,9 @@ int mmad_conv3d_fwd(const mmad_conv_desc* d, int dtype, const void* x, const voi
   if (dtype != MMAD_F32 && dtype != MMAD_BF16) return MMAD_EBADDTYPE;
   if (!x || !wp || !y) return MMAD_ENULL;
   if (!al16(x, wp, y)) return MMAD_EBADSHAPE;
-  if (unfolded(d) && mmad_stem::fwd_ok(d, dtype) && stem_kernel_on())
-    return mmad_stem::fwd(d, x, wp, bias, y, stats, stream);
   const Geom g = fwd_geom(d, dtype);
-  if (!geom_ok(g, dtype)) return MMAD_EUNSUPPORTED;
-  if (!unfolded(d) && use_lattice(g, dtype))
-    return mmad_lattice::fwd(patch_geo(g), x, wp, bias, y, stats, stream);
-  if (!unfolded(d) && use_lattice8(g, dtype))
-    return mmad_lattice8::fwd(patch_geo(g), x, wp, bias, y, stats, stream);
-  if (!unfolded(d) && use_patch(g, dtype))
-    return mmad_patch::fwd(patch_geo(g), x, wp, bias, y, stats, stream);
-  if (!unfolded(d) && use_s2(g, dtype))
-    return mmad_s2::fwd(patch_geo(g), g.sd, g.sh, g.sw, x, wp, bias, y, stats, stream);
-  if (mmad_pw::fwd_ok(d, dtype)) return mmad_pw::fwd(d, x, wp, bias, y, stats, stream);
-  return run_igemm<FWD>(g, dtype, g.M, 1, x, wp, bias, y, stats, as_stream(stream));
+  return launch_route(resolve(d, g, dtype, EPI_NONE), d, g, dtype, patch_geo(g), x, wp, bias, y,
+                      stats, stream);
 }
 
 int mmad_conv3d_fwd_ex(const mmad_conv_desc* d, int dtype, const void* x, const void* wp,
@@ -1803,31 +1860,11 @@ int mmad_conv3d_fwd_ex(const mmad_conv_desc* d, int dtype, const void* x, const 
   if (!x || !wp || !y) return MMAD_ENULL;
   if (!al16(x, wp, y) || !al16(res)) return MMAD_EBADSHAPE;
   if (res == nullptr && !relu) return mmad_conv3d_fwd(d, dtype, x, wp, bias, y, stats, stream);
-  if (unfolded(d)) return MMAD_EUNSUPPORTED;     // the stem keeps its own epilogue
   Geom g = fwd_geom(d, dtype);
-  if (!geom_ok(g, dtype)) return MMAD_EUNSUPPORTED;
   g.res = res;
   g.relu = relu ? 1 : 0;
-  if (use_lattice(g, dtype) || use_lattice8(g, dtype)) {
-    mmad_patch::Geo q = patch_geo(g);
-    q.res = res;
-    q.relu = g.relu;
-    return use_lattice(g, dtype) ? mmad_lattice::fwd(q, x, wp, bias, y, stats, stream)
-                                 : mmad_lattice8::fwd(q, x, wp, bias, y, stats, stream);
-  }
-  if (use_patch(g, dtype)) {
-    mmad_patch::Geo q = patch_geo(g);
-    q.res = res;
-    q.relu = g.relu;
-    return mmad_patch::fwd(q, x, wp, bias, y, stats, stream);
-  }
-  if (use_s2(g, dtype)) {
-    mmad_patch::Geo q = patch_geo(g);
-    q.res = res;
-    q.relu = g.relu;
-    return mmad_s2::fwd(q, g.sd, g.sh, g.sw, x, wp, bias, y, stats, stream);
-  }
-  return run_igemm<FWD>(g, dtype, g.M, 1, x, wp, bias, y, stats, as_stream(stream));
+  return launch_route(resolve(d, g, dtype, EPI_RES), d, g, dtype, patch_geo(g), x, wp, bias, y,
+                      stats, stream);
 }
 
 int mmad_conv3d_dgrad(const mmad_conv_desc* d, int dtype, const void* dy, const void* wpt,
@@ -1843,15 +1880,8 @@ int mmad_conv3d_dgrad(const mmad_conv_desc* d, int dtype, const void* dy, const 
   }
   if (dgrad_as_fwd(d)) {
     const Geom gf = dgrad_fwd_geom(d, dtype);
-    if (!geom_ok(gf, dtype)) return MMAD_EUNSUPPORTED;
-    if (use_lattice(gf, dtype))
-      return mmad_lattice::fwd(patch_geo(gf), dy, wpt, nullptr, dx, nullptr, stream);
-    if (use_lattice8(gf, dtype))
-      return mmad_lattice8::fwd(patch_geo(gf), dy, wpt, nullptr, dx, nullptr, stream);
-    if (use_patch(gf, dtype))
-      return mmad_patch::fwd(patch_geo(gf), dy, wpt, nullptr, dx, nullptr, stream);
-    return run_igemm<FWD>(gf, dtype, gf.M, 1, dy, wpt, nullptr, dx, nullptr,
-                          as_stream(stream));
+    return launch_route(resolve(nullptr, gf, dtype, EPI_NONE), nullptr, gf, dtype, patch_geo(gf),
+                        dy, wpt, nullptr, dx, nullptr, stream);
   }
   if (dtype == MMAD_BF16 && mmad_s2::dgrad_ok(d)) return mmad_s2::dgrad(d, dy, wpt, dx, stream);
   const Geom g = dgrad_geom(d, dtype);
@@ -1871,36 +1901,13 @@ int mmad_conv3d_dgrad(const mmad_conv_desc* d, int dtype, const void* dy, const 
                           as_stream(stream));
 }
 
-// dgrad routes whose epilogue also writes the BN-backward partial sums of the BN+ReLU that
-// produced the conv's input (bnsum.h): 1 = the plane-pair residue-class kernel (layer4),
-// 2 = the dilation-2 residue-class kernel (layer3), 3 = the patch conv (layer2's 128-channel
-// stride-1 conv; not its persistent z-walking form)
-static int bnsum_route(const mmad_conv_desc* d, int dtype, mmad_patch::Geo* qo) {
-  if (dtype != MMAD_BF16 || !desc_ok(d) || unfolded(d) || !dgrad_as_fwd(d)) return 0;
-  if (mmad_pw::ok(d, dtype)) return 0;
-  const Geom gf = dgrad_fwd_geom(d, dtype);
-  if (!geom_ok(gf, dtype)) return 0;
-  const mmad_patch::Geo q = patch_geo(gf);
-  int route = 0;
-  if (use_lattice(gf, dtype)) {
-    if (!mmad_lattice5::ok(q) && mmad_lattice_zp::ok(q)) route = 1;
-  } else if (use_lattice8(gf, dtype)) {
-    route = 2;
-  } else if (use_patch(gf, dtype) && !mmad_patchz::ok(q)) {
-    route = 3;
-  }
-  if (route) *qo = q;
-  return route;
-}
-
+// the stride-1 dgrad whose epilogue also writes the BN-backward partial sums of the BN+ReLU
+// that produced the conv's input (bnsum.h), on the leaves that have it: the plane-pair
+// residue-class kernel (layer4), the dilation-2 one (layer3) and the patch conv (layer2's
+// 128-channel stride-1 conv; not its z-walking form)
 int64_t mmad_conv3d_dgrad_bnsum_rows(const mmad_conv_desc* d, int dtype) {
-  mmad_patch::Geo q{};
-  switch (bnsum_route(d, dtype, &q)) {
-    case 1: return mmad_lattice_zp::tiles(q);
-    case 2: return mmad_lattice8::tiles(q);
-    case 3: return mmad_patch::tiles(q);
-    default: return -1;
-  }
+  Geom gf{};
+  return dgrad_fwd_route(d, dtype, EPI_BNSUM, &gf).tiles;
 }
 
 int mmad_conv3d_dgrad_bnsum(const mmad_conv_desc* d, int dtype, const void* dy, const void* wpt,
@@ -1908,37 +1915,17 @@ int mmad_conv3d_dgrad_bnsum(const mmad_conv_desc* d, int dtype, const void* dy, 
                             const float* mean, const float* invstd, float* parts, void* stream) {
   if (!dy || !wpt || !dx || !y || !scale || !shift || !mean || !invstd || !parts)
     return MMAD_ENULL;
-  mmad_patch::Geo q{};
-  const int route = bnsum_route(d, dtype, &q);
-  if (route == 0) return MMAD_EUNSUPPORTED;
+  Geom gf{};
+  const Route r = dgrad_fwd_route(d, dtype, EPI_BNSUM, &gf);
+  if (r.leaf == NONE) return MMAD_EUNSUPPORTED;
   if (((uintptr_t)scale | (uintptr_t)shift | (uintptr_t)mean | (uintptr_t)invstd) & 15)
     return MMAD_EBADSHAPE;                        // (16-byte constant loads)
   if (!al16(dy, wpt, dx) || !al16(y)) return MMAD_EBADSHAPE;
+  mmad_patch::Geo q = patch_geo(gf);
   q.bny = y;
   q.bnsc = scale; q.bnsh = shift; q.bnmu = mean; q.bnis = invstd;
   q.bnparts = parts;
-  switch (route) {
-    case 1: return mmad_lattice_zp::fwd(q, dy, wpt, nullptr, dx, nullptr, stream);
-    case 2: return mmad_lattice8::fwd(q, dy, wpt, nullptr, dx, nullptr, stream);
-    default: return mmad_patch::fwd(q, dy, wpt, nullptr, dx, nullptr, stream);
-  }
-}
-
-int64_t mmad_conv3d_wgrad_workspace(const mmad_conv_desc* d, int dtype) {
-  if (!desc_ok(d)) return -1;
-  const Geom g = fwd_geom(d, dtype);
-  const WSplit sp = wgrad_split(g, dtype);
-  int64_t slabs = (int64_t)sp.splits * g.Nd * g.K * 4;
-  if (!unfolded(d) && use_lattice_wgrad(g, dtype))
-    slabs = std::max<int64_t>(slabs, mmad_lattice::wgrad_workspace(patch_geo(g)));
-  if (!unfolded(d) && use_pwgrad(g, dtype))
-    slabs = std::max<int64_t>(slabs, mmad_pwgrad::workspace(patch_geo(g)));
-  if (!unfolded(d) && mmad_pw::wgrad_ok(d, dtype))
-    slabs = std::max<int64_t>(slabs, mmad_pw::wgrad_splits(d) * g.Nd * g.K * 4);
-  if (unfolded(d) && mmad_stem::fwd_ok(d, dtype) && stem_kernel_on())
-    slabs = std::max<int64_t>(slabs, mmad_stem::wgrad_blocks(d) * g.Nd * g.K * 4);
-  const int64_t parts = (int64_t)1024 * 2 * g.Nd * 4;   // bias-gradient column sums
-  return std::max(slabs, parts);
+  return launch_route(r, nullptr, gf, dtype, q, dy, wpt, nullptr, dx, nullptr, stream);
 }
 
 int mmad_colsum_ws(int dtype, int64_t m, int c, const void* y, float* parts, float* out,
@@ -1963,11 +1950,42 @@ int fork_stream(hipStream_t st, hipStream_t rst) {
   return hip_status(hipStreamWaitEvent(rst, ev[dev], 0));
 }
 
+// ---- the weight-gradient plan --------------------------------------------------------------
+// The kernels that write a conv's split-K slabs, in precedence order: the first leg that
+// takes the conv runs it (conv3d_wgrad), and the workspace query sizes for every leg that
+// could (mmad_conv3d_wgrad_workspace), so a variant switched between the two stays safe.
+enum WLeg { W_STEM, W_PWGRAD, W_LATTICE5, W_LATTICE, W_PW, W_IGEMM };
+// workspace bytes of a leg's slabs, -1 where the leg does not take the conv
+int64_t wleg_workspace(int leg, const mmad_conv_desc* d, const Geom& g, const mmad_patch::Geo& q,
+                       int dtype) {
+  const bool u = unfolded(d);
+  const bool s1 = !u && dtype == MMAD_BF16 && g.sd == 1 && g.sh == 1 && g.sw == 1;
+  const int64_t slab = (int64_t)g.Nd * g.K * 4;
+  switch (leg) {
+    case W_STEM:
+      return u && mmad_stem::fwd_ok(d, dtype) && stem_kernel_on() && g.K == 392
+                 ? mmad_stem::wgrad_blocks(d) * slab : -1;
+    case W_PWGRAD: return s1 && mmad_pwgrad::ok(q) ? mmad_pwgrad::workspace(q) : -1;
+    case W_LATTICE5: return s1 && mmad_lattice5::wgrad_ok(q) ? mmad_lattice5::wgrad_workspace(q) : -1;
+    case W_LATTICE: return s1 && mmad_lattice::wgrad_ok(q) ? mmad_lattice::wgrad_workspace(q) : -1;
+    // (bf16 1x1x1 and stride-2 3^3: pw_wgrad_kernel, pointwise.hip; what stays on wgrad_kernel
+    // is fp32 and the geometries the others decline)
+    case W_PW: return !u && mmad_pw::wgrad_ok(d, dtype) ? mmad_pw::wgrad_splits(d) * slab : -1;
+    default: return wgrad_split(g, dtype).splits * slab;
+  }
+}
+
+// how a leg's slabs become dW: 16-slab group sums first (the stem: one slab per block, so no
+// thread walks them all), transposing (whole [ci][taps] runs of dW: scattered 4-byte stores
+// from an element-wise reduce cost ~2x in partial-line writes), wide, element-wise
+enum RKind { R_STEM, R_T, R_WIDE, R_ELEM };
+struct WPlan { int splits; RKind kind; bool deferrable; };
+
 // weight gradient: the split-K kernel on `st`, then the slab reduction (and the bias
 // gradient) on `rst` -- a second stream lets the memory-bound reduction overlap the
 // latency-bound BN backward kernels that follow on `st`
 // defer (non-null, no bias): the slab reduction is recorded there instead of launched when
-// the path has one (defer->kind = KIND_NONE: everything ran inline)
+// the leg's plan allows (defer->kind = KIND_NONE: everything ran inline)
 int conv3d_wgrad(const mmad_conv_desc* d, int dtype, const void* x, const void* dy, float* dw,
                  float* dbias, void* workspace, hipStream_t st, hipStream_t rst,
                  int raw_dtype = -1, mmad_reduce::Job* defer = nullptr) {
@@ -1981,140 +1999,110 @@ int conv3d_wgrad(const mmad_conv_desc* d, int dtype, const void* x, const void* 
   if (!al16(x, dy, workspace)) return MMAD_EBADSHAPE;
   const Geom g = fwd_geom(d, dtype);
   if (!geom_ok(g, dtype) || g.Nd % (dtype == MMAD_BF16 ? 8 : 4)) return MMAD_EUNSUPPORTED;
-  void* const stream = st;
-  void* const rstream = rst;
-  int rc;
-  // (the bf16 1x1x1 and stride-2 3^3 weight gradients leave below for pw_wgrad_kernel,
-  // pointwise.hip; what stays on wgrad_kernel is fp32 and the geometries it declines)
-  if (raw_dtype >= 0 && !(unfolded(d) && mmad_stem::fwd_ok(d, dtype) && g.K == 392))
-    return MMAD_EUNSUPPORTED;                    // raw input: the stem kernel or nothing
-  if (unfolded(d) && mmad_stem::fwd_ok(d, dtype) && (stem_kernel_on() || raw_dtype >= 0) &&
-      g.K == 392) {
-    rc = mmad_stem::wgrad(d, x, dy, (float*)workspace, stream, raw_dtype);
-    if (rc) return rc;
-    // (one slab per block: sum 16-slab groups in place first, so no thread walks them all)
-    const int nb = (int)mmad_stem::wgrad_blocks(d);
-    const int64_t total = (int64_t)g.Nd * g.K;
-    constexpr int G = 16;
-    static_assert(G == mmad_reduce::STEM_G, "the deferred stem reduction sums the same groups");
-    if (defer != nullptr && cdiv(nb, G) <= 32) {
-      mmad_reduce::Job& j = *defer;
-      j.ws = (const float*)workspace; j.dw = dw; j.splits = nb; j.nd = g.Nd; j.k = g.K;
-      j.cs = g.Cs; j.taps = g.taps; j.tper = d->kw; j.kind = mmad_reduce::KIND_STEM;
-      j.gx = (int)cdiv(total, 64); j.gy = 1; j.gz = 1;
-      return MMAD_OK;
-    }
-    if (rst != st && (rc = fork_stream(st, rst))) return rc;
-    hipLaunchKernelGGL(slab_group_sum_kernel, dim3(grid_for(total * cdiv(nb, G))), dim3(256), 0,
-                       rst, (float*)workspace, nb, total, G);
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(grid_for(total)), dim3(256), 0, rst,
-                       (const float*)workspace, dw, nb, g.Nd, g.K, g.Cs, g.cs_shift, g.taps,
-                       d->kw, G);
-    rc = launch_status();
-    if (rc) return rc;
-    if (dbias) return mmad_colsum_ws(dtype, g.M, g.Nd, dy, (float*)workspace, dbias, rstream);
-    return MMAD_OK;
-  }
-  if (!unfolded(d) && (use_lattice_wgrad(g, dtype) || use_pwgrad(g, dtype))) {
-    int splits = 0;
-    rc = use_pwgrad(g, dtype)
-             ? mmad_pwgrad::wgrad(patch_geo(g), x, dy, (float*)workspace, &splits, stream)
-             : mmad_lattice::wgrad(patch_geo(g), x, dy, (float*)workspace, &splits, stream);
-    if (rc) return rc;
-    if (defer != nullptr) {
-      *defer = plan_reduce_t((const float*)workspace, dw, splits, g.Nd, g.K, g.Cs, g.taps);
-      return MMAD_OK;
-    }
-    if (rst != st && (rc = fork_stream(st, rst))) return rc;
-    rc = launch_reduce_t((const float*)workspace, dw, splits, g.Nd, g.K, g.Cs, g.taps, rst);
-    if (rc) return rc;
-    if (dbias) return mmad_colsum_ws(dtype, g.M, g.Nd, dy, (float*)workspace, dbias, rstream);
-    return MMAD_OK;
-  }
-  if (!unfolded(d) && mmad_pw::wgrad_ok(d, dtype)) {
-    // 1x1x1 (the shortcuts) and the stride-2 3^3 conv: the pointwise split-K GEMM, then the
-    // wide (1^3) or transposing (3^3) slab reduction
-    rc = mmad_pw::wgrad(d, x, dy, (float*)workspace, st);
-    if (rc) return rc;
-    const int splits = (int)mmad_pw::wgrad_splits(d);
-    const int64_t total = (int64_t)g.Nd * g.K;
-    if (g.taps > 1) {
-      if (defer != nullptr) {
-        *defer = plan_reduce_t((const float*)workspace, dw, splits, g.Nd, g.K, g.Cs, g.taps);
-        return MMAD_OK;
-      }
-      if (rst != st && (rc = fork_stream(st, rst))) return rc;
-      rc = launch_reduce_t((const float*)workspace, dw, splits, g.Nd, g.K, g.Cs, g.taps, rst);
-      if (rc) return rc;
-      if (dbias) return mmad_colsum_ws(dtype, g.M, g.Nd, dy, (float*)workspace, dbias, rstream);
-      return MMAD_OK;
-    }
-    if (defer != nullptr && ((uintptr_t)dw & 15) == 0) {
-      mmad_reduce::Job& j = *defer;
-      j.ws = (const float*)workspace; j.dw = dw; j.splits = splits; j.nd = g.Nd;
-      j.k = g.K; j.cs = g.Cs; j.taps = 1; j.kind = mmad_reduce::KIND_WIDE;
-      j.gx = (int)cdiv(total, 256); j.gy = 1; j.gz = 1;
-      return MMAD_OK;
-    }
-    if (rst != st && (rc = fork_stream(st, rst))) return rc;
-    hipLaunchKernelGGL(wgrad_reduce_wide_kernel, dim3((unsigned)cdiv(total, 256)), dim3(256), 0,
-                       rst, (const float*)workspace, dw, splits, g.Nd, g.K, g.Cs, g.cs_shift,
-                       g.taps, 0, 1);
-    rc = launch_status();
-    if (rc) return rc;
-    if (dbias) return mmad_colsum_ws(dtype, g.M, g.Nd, dy, (float*)workspace, dbias, rstream);
-    return MMAD_OK;
-  }
-  const WSplit sp = wgrad_split(g, dtype);
-  if (dtype == MMAD_BF16)
-    rc = sp.bmw == 256 ? (wgrad_big(g, dtype) == 3
-                              ? launch_wgrad_k<u16, 256, 32, 3, 256, 2, 4>(g, sp, x, dy,
-                                                                          (float*)workspace, st)
-                              : launch_wgrad_k<u16, 256, 32, 2, 256, 2, 4>(g, sp, x, dy,
-                                                                          (float*)workspace, st))
-       : sp.bmw == 64 ? launch_wgrad<u16, 64>(g, sp, x, dy, (float*)workspace, st)
-                      : launch_wgrad<u16, 128>(g, sp, x, dy, (float*)workspace, st);
-  else
-    rc = sp.bmw == 64 ? launch_wgrad<float, 64>(g, sp, x, dy, (float*)workspace, st)
-                      : launch_wgrad<float, 128>(g, sp, x, dy, (float*)workspace, st);
-  if (rc) return rc;
+  const mmad_patch::Geo q = patch_geo(g);
+  float* const ws = (float*)workspace;
+  const bool u = unfolded(d);
   const int64_t total = (int64_t)g.Nd * g.K;
-  if (defer != nullptr && !unfolded(d)) {
-    if (g.taps > 1 && g.taps <= 32) {
-      *defer = plan_reduce_t((const float*)workspace, dw, sp.splits, g.Nd, g.K, g.Cs, g.taps);
+  const bool dw16 = ((uintptr_t)dw & 15) == 0;
+  constexpr int G = mmad_reduce::STEM_G;         // the deferred stem reduction sums the same groups
+
+  // 1. the kernel: the first leg that takes the conv (raw input: the stem or nothing)
+  int leg = W_STEM;
+  while (leg < W_IGEMM && wleg_workspace(leg, d, g, q, dtype) < 0) ++leg;
+  if (raw_dtype >= 0 && leg != W_STEM) return MMAD_EUNSUPPORTED;
+
+  // 2. its launch, slab count and reduction
+  WPlan p{0, R_T, true};
+  int rc;
+  switch (leg) {
+    case W_STEM:
+      rc = mmad_stem::wgrad(d, x, dy, ws, st, raw_dtype);
+      p.splits = (int)mmad_stem::wgrad_blocks(d);
+      p.kind = R_STEM;
+      p.deferrable = cdiv(p.splits, G) <= 32;
+      break;
+    case W_PWGRAD: rc = mmad_pwgrad::wgrad(q, x, dy, ws, &p.splits, st); break;
+    case W_LATTICE5: rc = mmad_lattice5::wgrad(q, x, dy, ws, &p.splits, st); break;
+    case W_LATTICE: rc = mmad_lattice::wgrad(q, x, dy, ws, &p.splits, st); break;
+    case W_PW:     // the stride-2 3^3 conv: transposing; 1x1x1 (the shortcuts): wide
+      rc = mmad_pw::wgrad(d, x, dy, ws, st);
+      p.splits = (int)mmad_pw::wgrad_splits(d);
+      if (g.taps == 1) { p.kind = R_WIDE; p.deferrable = dw16; }
+      break;
+    default: {
+      const WSplit sp = wgrad_split(g, dtype);
+      if (dtype == MMAD_BF16)
+        rc = sp.bmw == 256 ? (wgrad_big(g, dtype) == 3
+                                  ? launch_wgrad_k<u16, 256, 32, 3, 256, 2, 4>(g, sp, x, dy, ws, st)
+                                  : launch_wgrad_k<u16, 256, 32, 2, 256, 2, 4>(g, sp, x, dy, ws, st))
+           : sp.bmw == 64 ? launch_wgrad<u16, 64>(g, sp, x, dy, ws, st)
+                          : launch_wgrad<u16, 128>(g, sp, x, dy, ws, st);
+      else
+        rc = sp.bmw == 64 ? launch_wgrad<float, 64>(g, sp, x, dy, ws, st)
+                          : launch_wgrad<float, 128>(g, sp, x, dy, ws, st);
+      const bool t = !u && g.taps > 1 && g.taps <= 32;
+      p.splits = sp.splits;
+      p.kind = t ? R_T : sp.splits >= 8 ? R_WIDE : R_ELEM;
+      p.deferrable = !u && (t || (g.taps == 1 && sp.splits >= 8 && total % 4 == 0 && dw16));
+    }
+  }
+  if (rc) return rc;
+
+  // 3. the reduction: recorded for the batched launch, or on `rst` now, then the bias
+  // column sums (which reuse the workspace) behind it
+  const int tper = u ? d->kw : 0;
+  if (defer != nullptr && p.deferrable) {
+    if (p.kind == R_T) {
+      *defer = plan_reduce_t(ws, dw, p.splits, g.Nd, g.K, g.Cs, g.taps);
       return MMAD_OK;
     }
-    if (g.taps == 1 && sp.splits >= 8 && total % 4 == 0 && ((uintptr_t)dw & 15) == 0) {
-      mmad_reduce::Job& j = *defer;
-      j.ws = (const float*)workspace; j.dw = dw; j.splits = sp.splits; j.nd = g.Nd;
-      j.k = g.K; j.cs = g.Cs; j.taps = 1; j.kind = mmad_reduce::KIND_WIDE;
-      j.gx = (int)cdiv(total, 256); j.gy = 1; j.gz = 1;
-      return MMAD_OK;
-    }
+    const bool stem = p.kind == R_STEM;          // else R_WIDE
+    mmad_reduce::Job& j = *defer;
+    j.ws = ws; j.dw = dw; j.splits = p.splits; j.nd = g.Nd; j.k = g.K; j.cs = g.Cs;
+    j.taps = g.taps; j.tper = tper;
+    j.kind = stem ? mmad_reduce::KIND_STEM : mmad_reduce::KIND_WIDE;
+    j.gx = (int)cdiv(total, stem ? 64 : 256); j.gy = 1; j.gz = 1;
+    return MMAD_OK;
   }
   if (rst != st && (rc = fork_stream(st, rst))) return rc;
-  // (the transposing reduce writes whole [ci][taps] runs of dW; scattered 4-byte dW stores
-  // from an element-wise reduce cost ~2x in partial-line writes)
-  if (!unfolded(d) && g.taps > 1 && g.taps <= 32) {
-    rc = launch_reduce_t((const float*)workspace, dw, sp.splits, g.Nd, g.K, g.Cs, g.taps, rst);
-    if (rc) return rc;
-  } else if (sp.splits >= 8)
-    hipLaunchKernelGGL(wgrad_reduce_wide_kernel, dim3((unsigned)cdiv(total, 256)), dim3(256), 0,
-                       rst, (const float*)workspace, dw, sp.splits, g.Nd, g.K, g.Cs, g.cs_shift,
-                       g.taps, unfolded(d) ? d->kw : 0, 1);
-  else
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(grid_for(total)), dim3(256), 0, rst,
-                       (const float*)workspace, dw, sp.splits, g.Nd, g.K, g.Cs, g.cs_shift,
-                       g.taps, unfolded(d) ? d->kw : 0, 1);
-  rc = launch_status();
+  switch (p.kind) {
+    case R_T:
+      rc = launch_reduce_t(ws, dw, p.splits, g.Nd, g.K, g.Cs, g.taps, rst);
+      break;
+    case R_WIDE:
+      hipLaunchKernelGGL(wgrad_reduce_wide_kernel, dim3((unsigned)cdiv(total, 256)), dim3(256), 0,
+                         rst, (const float*)ws, dw, p.splits, g.Nd, g.K, g.Cs, g.cs_shift, g.taps,
+                         tper, 1);
+      rc = launch_status();
+      break;
+    case R_STEM:
+      hipLaunchKernelGGL(slab_group_sum_kernel, dim3(grid_for(total * cdiv(p.splits, G))),
+                         dim3(256), 0, rst, ws, p.splits, total, G);
+      [[fallthrough]];
+    case R_ELEM:
+      hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(grid_for(total)), dim3(256), 0, rst,
+                         (const float*)ws, dw, p.splits, g.Nd, g.K, g.Cs, g.cs_shift, g.taps,
+                         tper, p.kind == R_STEM ? G : 1);
+      rc = launch_status();
+  }
   if (rc) return rc;
-  if (dbias) return mmad_colsum_ws(dtype, g.M, g.Nd, dy, (float*)workspace, dbias, rstream);
+  if (dbias) return mmad_colsum_ws(dtype, g.M, g.Nd, dy, ws, dbias, rst);
   return MMAD_OK;
 }
 
 }  // namespace
 
 extern "C" {
+
+int64_t mmad_conv3d_wgrad_workspace(const mmad_conv_desc* d, int dtype) {
+  if (!desc_ok(d)) return -1;
+  const Geom g = fwd_geom(d, dtype);
+  const mmad_patch::Geo q = patch_geo(g);
+  int64_t bytes = (int64_t)1024 * 2 * g.Nd * 4;   // bias-gradient column sums
+  for (int leg = W_STEM; leg <= W_IGEMM; ++leg)
+    bytes = std::max(bytes, wleg_workspace(leg, d, g, q, dtype));
+  return bytes;
+}
 
 int mmad_conv3d_wgrad(const mmad_conv_desc* d, int dtype, const void* x, const void* dy,
                       float* dw, float* dbias, void* workspace, void* stream) {

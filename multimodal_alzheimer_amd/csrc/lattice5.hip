@@ -829,6 +829,7 @@ int64_t tiles(const mmad_patch::Geo& q) { return (int64_t)q.nb * (q.dd * q.dd * 
 int fwd(const mmad_patch::Geo& q, const void* src, const void* wp, const float* bias, void* dst,
         float* stats, void* stream) {
   if (!mmad_lattice5::ok(q)) return MMAD_EUNSUPPORTED;
+  if (q.bny != nullptr) return MMAD_EUNSUPPORTED;   // no BN-sum epilogue in this kernel
   static const bool attr = hipFuncSetAttribute((const void*)lattice5_conv_kernel,
                                                hipFuncAttributeMaxDynamicSharedMemorySize,
                                                LDS) == hipSuccess;

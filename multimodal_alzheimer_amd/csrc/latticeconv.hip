@@ -761,8 +761,6 @@ int lattice_mode() {
 
 namespace mmad_lattice {
 
-int64_t tiles(const mmad_patch::Geo& q);
-
 int set_mode(int v) {
   const int prev = lattice_mode();
   if (v >= 0) g_lattice_mode.store(v, std::memory_order_relaxed);
@@ -792,8 +790,9 @@ static int planes(const mmad_patch::Geo& q) {
   return exact(q) ? S : (q.Ds + q.dd - 1) / q.dd;
 }
 
-bool ok(const mmad_patch::Geo& q) {
-  if (mmad_lattice5::ok(q)) return true;          // 5d^3 grids (lattice5.hip)
+// fill_tiles: M tiles of the launch that would run q -- tiles(q), or the plane-pair form's
+// where the route resolver (conv.hip) prefers that
+bool ok(const mmad_patch::Geo& q, int64_t fill_tiles) {
   if (lattice_mode() <= 0) return false;
   const int d = q.dd;
   if (q.KD != 3 || q.KH != 3 || q.KW != 3 || q.dh != d || q.dw != d || d < 2) return false;
@@ -808,16 +807,13 @@ bool ok(const mmad_patch::Geo& q) {
     return false;
   // one 512-thread block per CU: tiles too few for the CUs even at 64 channels leave the
   // row-gather implicit GEMM (more, smaller blocks) ahead
-  if (lattice_mode() == 1 && mmad_lattice::tiles(q) * (q.Nd / 64) < 256) return false;
+  if (lattice_mode() == 1 && fill_tiles * (q.Nd / 64) < 256) return false;
   return (int64_t)q.nb * E * E * E * q.Cs < (int64_t(1) << 40);
 }
 
 int64_t tiles(const mmad_patch::Geo& q) {
-  if (mmad_lattice5::ok(q)) return mmad_lattice5::tiles(q);
-  if (exact(q) && mmad_lattice_zp::ok(q)) return mmad_lattice_zp::tiles(q);
   return (int64_t)q.nb * q.dd * q.dd * q.dd / NS * planes(q);
 }
-
 
 int wgrad_splits(const mmad_patch::Geo& q) {
   const int64_t tiles = (int64_t)(q.Cs / KC) * (q.Nd / 64);
@@ -840,7 +836,6 @@ int lattice_wgrad_mode() {
 }
 
 bool wgrad_ok(const mmad_patch::Geo& q) {
-  if (mmad_lattice5::wgrad_ok(q)) return true;    // 5d^3 grids (lattice5.hip)
   if (lattice_mode() <= 0 || lattice_wgrad_mode() <= 0) return false;
   const int d = q.dd;
   if (q.KD != 3 || q.KH != 3 || q.KW != 3 || q.dh != d || q.dw != d || d < 2) return false;
@@ -855,13 +850,11 @@ bool wgrad_ok(const mmad_patch::Geo& q) {
 }
 
 int64_t wgrad_workspace(const mmad_patch::Geo& q) {
-  if (mmad_lattice5::wgrad_ok(q)) return mmad_lattice5::wgrad_workspace(q);
   return (int64_t)wgrad_splits(q) * q.Nd * 27 * q.Cs * 4;
 }
 
 int wgrad(const mmad_patch::Geo& q, const void* x, const void* dy, float* ws, int* splits,
           void* stream) {
-  if (mmad_lattice5::wgrad_ok(q)) return mmad_lattice5::wgrad(q, x, dy, ws, splits, stream);
   if (!wgrad_ok(q)) return MMAD_EUNSUPPORTED;
   static const bool attr =
       hipFuncSetAttribute((const void*)lattice_wgrad_kernel<4>,
@@ -889,11 +882,9 @@ int wgrad(const mmad_patch::Geo& q, const void* x, const void* dy, float* ws, in
 
 int fwd(const mmad_patch::Geo& q, const void* src, const void* wp, const float* bias,
         void* dst, float* stats, void* stream) {
-  if (mmad_lattice5::ok(q)) return mmad_lattice5::fwd(q, src, wp, bias, dst, stats, stream);
-  if (!mmad_lattice::ok(q)) return MMAD_EUNSUPPORTED;
+  if (!mmad_lattice::ok(q, mmad_lattice::tiles(q))) return MMAD_EUNSUPPORTED;
+  if (q.bny != nullptr) return MMAD_EUNSUPPORTED;   // no BN-sum epilogue in this kernel
   const bool rag = !exact(q);
-  if (!rag && mmad_lattice_zp::ok(q))
-    return mmad_lattice_zp::fwd(q, src, wp, bias, dst, stats, stream);
   static const bool attr =
       hipFuncSetAttribute((const void*)lattice_conv_kernel<4, false>,
                           hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES) == hipSuccess &&

@@ -33,14 +33,12 @@
 //    tap are template constants in the main loop), as in latticeconv.hip.
 #include <atomic>
 #include <cstdlib>
-#include <cstring>
 #include <type_traits>
 #include <utility>
 
 #include "bnsum.h"
 #include "common.h"
 #include "patchconv.h"
-#include "pointwise.h"
 
 namespace {
 
@@ -540,8 +538,15 @@ int zp_mode() {
 
 namespace mmad_lattice_zp {
 
-// the caller (mmad_lattice) has checked the residue-class geometry; this form needs d = 4
-// (16^3 grids, 64 classes per sample) and enough tiles to give every CU one
+int set_mode(int v) {
+  const int prev = zp_mode();
+  if (v >= 0) g_zp_mode.store(v, std::memory_order_relaxed);
+  return prev;
+}
+
+// the route resolver (conv.hip) checks the residue-class geometry with mmad_lattice::ok; on
+// top of it this form needs d = 4 (16^3 grids, 64 classes per sample) and enough tiles to
+// give every CU one
 bool ok(const mmad_patch::Geo& q) {
   if (zp_mode() <= 0 || q.dd != 4 || q.Cs % KC || q.Nd % 64) return false;
   if (q.Ds != 16 || q.Hs != 16 || q.Ws != 16 || q.Dd != 16 || q.Hd != 16 || q.Wd != 16)
@@ -597,19 +602,3 @@ int fwd(const mmad_patch::Geo& q, const void* src, const void* wp, const float* 
 }
 
 }  // namespace mmad_lattice_zp
-
-extern "C" int mmad_set_kernel_variant(const char* name, int value) {
-  if (name == nullptr) return -1;
-  if (std::strcmp(name, "lattice_zp") == 0) {
-    const int prev = zp_mode();
-    if (value >= 0) g_zp_mode.store(value, std::memory_order_relaxed);
-    return prev;
-  }
-  if (std::strcmp(name, "lattice") == 0) return mmad_lattice::set_mode(value);
-  if (std::strcmp(name, "lattice8") == 0) return mmad_lattice8::set_mode(value);
-  if (std::strcmp(name, "lattice5") == 0) return mmad_lattice5::set_mode(value);
-  if (std::strcmp(name, "pool_run") == 0) return mmad_pool::set_run_mode(value);
-  if (std::strcmp(name, "patchz") == 0) return mmad_patchz::set_mode(value);
-  if (std::strcmp(name, "pw_wg3_dedup") == 0) return mmad_pw::set_wg3_dedup(value);
-  return -1;
-}

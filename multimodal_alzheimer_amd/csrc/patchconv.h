@@ -1,11 +1,14 @@
-// Patch-resident stride-1 3D convolution for narrow layers (bf16), internal to
-// libmmad_hip.so: mmad_conv3d_fwd / mmad_conv3d_dgrad route matching geometries here
-// (see patchconv.hip for the design).
+// The stride-1 / stride-2 bf16 conv kernels beside the implicit GEMM, internal to
+// libmmad_hip.so.  Each namespace answers for its own kernel only -- ok() whether it handles a
+// geometry, tiles() the rows of the BN partial buffer its launch writes, fwd() that launch
+// (MMAD_EUNSUPPORTED for an epilogue field the kernel does not implement).  Which of them
+// runs a conv, and in what precedence, is decided in one place: resolve() in conv.hip.
 #pragma once
 #include <stdint.h>
 
 #include "../../include/mmad.h"
 
+// Patch-resident stride-1 3D convolution for narrow layers (see patchconv.hip for the design).
 namespace mmad_patch {
 // stride-1 conv over NDHWC bf16 volumes; weights packed [Nd][Kpad] with k = tap*Cs + ci
 struct Geo {
@@ -33,7 +36,7 @@ int fwd(const Geo& g, const void* src, const void* wp, const float* bias, void* 
 }  // namespace mmad_patch
 
 // Persistent z-walking form of the patch conv for 64-channel inputs on grids of 4 x 8 x 8
-// boxes (patchz.hip, layer1): mmad_patch::fwd / tiles route to it when ok().
+// boxes (patchz.hip, layer1): ahead of mmad_patch where both are ok().  No BN-sum epilogue.
 namespace mmad_patchz {
 int set_mode(int v);              // MMAD_PATCHZ at run time; returns the previous mode
 bool ok(const mmad_patch::Geo& g);
@@ -42,11 +45,14 @@ int fwd(const mmad_patch::Geo& g, const void* src, const void* wp, const float* 
         float* stats, void* stream);
 }  // namespace mmad_patchz
 
-// Residue-class conv for dilated 3^3 convs on a 4d^3 grid (latticeconv.hip): same geometry
-// record, packed weights and partial-sum layout as the patch kernel.
+// Residue-class conv for dilated 3^3 convs on a 4d^3 or ragged grid (latticeconv.hip): same
+// geometry record, packed weights and partial-sum layout as the patch kernel.  No BN-sum
+// epilogue.
 namespace mmad_lattice {
 int set_mode(int v);              // MMAD_LATTICE at run time; returns the previous mode
-bool ok(const mmad_patch::Geo& g);
+// fill_tiles: M tiles of the launch that would run g (tiles(g), or mmad_lattice_zp's where
+// that form applies) for the fill-the-CUs rule of mode 1
+bool ok(const mmad_patch::Geo& g, int64_t fill_tiles);
 int64_t tiles(const mmad_patch::Geo& g);
 int fwd(const mmad_patch::Geo& g, const void* src, const void* wp, const float* bias, void* dst,
         float* stats, void* stream);
@@ -60,7 +66,7 @@ int wgrad(const mmad_patch::Geo& g, const void* x, const void* dy, float* ws, in
 
 // Stride-2 3^3 conv forward on parity sub-patches (s2conv.hip, layer2.0.conv1: 64 input
 // channels, even input extents, whole 2 x 8 x 8 output boxes); strides passed separately
-// (Geo has none).  One BN partial-sum row per output box.
+// (Geo has none).  One BN partial-sum row per output box.  No BN-sum epilogue.
 namespace mmad_s2 {
 bool ok(const mmad_patch::Geo& g, int sd, int sh, int sw);
 int64_t tiles(const mmad_patch::Geo& g);
@@ -73,24 +79,26 @@ int dgrad(const mmad_conv_desc* d, const void* dy, const void* wpt, void* dx, vo
 }  // namespace mmad_s2
 
 // Plane-pair form of the residue-class conv for d = 4 (latticezp.hip): two z-planes of 16
-// subs per tile, one wave per SIMD; mmad_lattice::fwd / tiles route to it when ok().
+// subs per tile, one wave per SIMD; ahead of mmad_lattice where both are ok() (its ok() adds
+// to mmad_lattice::ok, which checks the residue-class geometry).
 namespace mmad_lattice_zp {
+int set_mode(int v);              // MMAD_LATTICE_ZP at run time; returns the previous mode
 bool ok(const mmad_patch::Geo& g);
 int64_t tiles(const mmad_patch::Geo& g);
 int fwd(const mmad_patch::Geo& g, const void* src, const void* wp, const float* bias, void* dst,
         float* stats, void* stream);
 }  // namespace mmad_lattice_zp
 
-// Residue-class conv on 5d^3 grids (lattice5.hip: config 5's 20^3 layer4, 5^3 sub-lattices):
-// mmad_lattice::ok / tiles / fwd route to it first.
+// Residue-class conv on 5d^3 grids (lattice5.hip: config 5's 20^3 layer4, 5^3 sub-lattices),
+// first among the residue-class kernels.  No BN-sum epilogue.
 namespace mmad_lattice5 {
 int set_mode(int v);              // MMAD_LATTICE5 at run time; returns the previous mode
 bool ok(const mmad_patch::Geo& g);
 int64_t tiles(const mmad_patch::Geo& g);
 int fwd(const mmad_patch::Geo& g, const void* src, const void* wp, const float* bias, void* dst,
         float* stats, void* stream);
-// weight gradient (mmad_lattice::wgrad_ok / wgrad_workspace / wgrad route to it first):
-// fp32 partial slabs [splits][Nd][27 * Cs]
+// weight gradient (ahead of mmad_lattice's in conv.hip's leg list): fp32 partial slabs
+// [splits][Nd][27 * Cs]
 bool wgrad_ok(const mmad_patch::Geo& g);
 int64_t wgrad_workspace(const mmad_patch::Geo& g);
 int wgrad(const mmad_patch::Geo& g, const void* x, const void* dy, float* ws, int* splits,

@@ -491,6 +491,7 @@ int64_t tiles(const mmad_patch::Geo& q) {
 int fwd(const mmad_patch::Geo& q, const void* src, const void* wp, const float* bias, void* dst,
         float* stats, void* stream) {
   if (!mmad_patchz::ok(q)) return MMAD_EUNSUPPORTED;
+  if (q.bny != nullptr) return MMAD_EUNSUPPORTED;   // no BN-sum epilogue in this kernel
   static const bool attr =
       hipFuncSetAttribute((const void*)patchz_conv_kernel,
                           hipFuncAttributeMaxDynamicSharedMemorySize, LDS) == hipSuccess;

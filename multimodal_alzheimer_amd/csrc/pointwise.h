@@ -1,5 +1,7 @@
-// 1x1x1 stride-1 conv input gradient as a hand-written MFMA GEMM (pointwise.hip), internal to
-// libmmad_hip.so.
+// The 1x1x1 convs (and the stride-2 3^3 weight gradient) as hand-written MFMA GEMMs
+// (pointwise.hip), internal to libmmad_hip.so: the PW leaf of conv.hip's resolve() (no
+// residual / ReLU epilogue), the W_PW leg of its weight-gradient plan, and the first choice of
+// mmad_conv3d_dgrad.
 #pragma once
 #include <stdint.h>
 

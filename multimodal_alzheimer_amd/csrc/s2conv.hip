@@ -604,6 +604,7 @@ int64_t tiles(const mmad_patch::Geo& q) {
 int fwd(const mmad_patch::Geo& q, int sd, int sh, int sw, const void* src, const void* wp,
         const float* bias, void* dst, float* stats, void* stream) {
   if (!ok(q, sd, sh, sw)) return MMAD_EUNSUPPORTED;
+  if (q.bny != nullptr) return MMAD_EUNSUPPORTED;   // no BN-sum epilogue in this kernel
   const int bn = q.Nd % 128 == 0 ? 128 : 64;
   S2G g{};
   g.Ds = q.Ds; g.Hs = q.Hs; g.Ws = q.Ws; g.Dd = q.Dd; g.Hd = q.Hd; g.Wd = q.Wd;

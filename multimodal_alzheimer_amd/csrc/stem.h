@@ -1,6 +1,7 @@
 // Dedicated MedicalNet stem convolution (conv1: Cin 1 -> 64, 7x7x7, stride 2, pad 3) on the
 // W-unfolded input (layout [n][di][hi][wo][8], see mmad_conv_unfold_input).  Internal to
-// libmmad_hip.so: mmad_conv3d_fwd routes a matching descriptor here.
+// libmmad_hip.so: the STEM leaf of conv.hip's resolve(), the first leg of its weight-gradient
+// plan.
 #pragma once
 #include <stdint.h>
 
