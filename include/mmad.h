@@ -61,6 +61,8 @@ const char* mmad_strerror(int status);
  * reference counterpart): "lattice_zp" = 1 plane-pair residue-class conv (default), 0 the
  * one-plane form, 2 plane-pair at any size; "lattice" / "lattice8" / "lattice5" = 1
  * residue-class convs where their tiles fill the CUs (default), 2 at any size, 0 off;
+ * "lattice8_xwalk" = 1 lattice8's x-walk form on the exact 16^3 grid (default), 0 the
+ * x-pair form that the ragged grids run (same bits);
  * "pool_run" = the stem BN+ReLU+max-pool forward: 2 the z-walking kernel (default), other
  * values the per-output rows kernel; "patchz" = 1 the persistent z-walking layer1 conv where
  * its work items fill the CUs (default), 2 at any size, 0 the per-box patch conv;

@@ -1650,6 +1650,7 @@ int mmad_set_kernel_variant(const char* name, int value) {
   if (std::strcmp(name, "lattice_zp") == 0) return mmad_lattice_zp::set_mode(value);
   if (std::strcmp(name, "lattice") == 0) return mmad_lattice::set_mode(value);
   if (std::strcmp(name, "lattice8") == 0) return mmad_lattice8::set_mode(value);
+  if (std::strcmp(name, "lattice8_xwalk") == 0) return mmad_lattice8::set_xwalk(value);
   if (std::strcmp(name, "lattice5") == 0) return mmad_lattice5::set_mode(value);
   if (std::strcmp(name, "pool_run") == 0) return mmad_pool::set_run_mode(value);
   if (std::strcmp(name, "patchz") == 0) return mmad_patchz::set_mode(value);

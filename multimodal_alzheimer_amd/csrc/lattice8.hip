@@ -11,17 +11,23 @@
 // is padding.  A stage is one input plane tz+kz (32 input channels, 32 KiB) and its 9 taps'
 // weights (64 output channels x 32 input channels = 4 KiB a tap), double-buffered: the next
 // stage's plane and weights load during this stage's MFMAs.
-//  * a 16-row MFMA fragment is 2 x-neighbouring positions x 8 classes: a y shift out of
-//    the plane drops the whole fragment (compile-time per wave row, skipped); an x shift
-//    out of the plane drops half the lanes, which then read a zero row (one select);
-//  * 8 waves = 4 x 2 wave tiles of 128 rows (two y rows of the plane) x 32 channels;
-//  * the loop walks (chunk, kz) stages with ky, kx = -1, 0, 1 inside, the next tap's
-//    fragment reads in flight during each tap's MFMAs, one barrier per stage;
+// Two forms of the 9-tap stage, one barrier a stage in both:
+//  * x-walk form (the exact 16^3 grid): a 16-row MFMA fragment is 2 y-neighbouring
+//    positions x 8 classes, so a kx shift moves whole fragments; 8 waves = 4 y pairs x 2
+//    channel halves, a wave walks its row pair along x: per ky row it reads the 8 fragments
+//    once, uses them for the three kx taps and leaves out the (x, kx) off the plane; the
+//    next row's fragments and the weights two taps ahead are read between the MFMAs;
+//  * x-pair form (ragged grids; the exact grid with MMAD_L8_XWALK=0): a fragment is 2
+//    x-neighbouring positions x 8 classes: a y shift out of the plane drops the whole
+//    fragment (compile-time per wave row, skipped); an x shift out of the plane drops half
+//    the lanes, which then read a zero row (one select); 8 waves = the 8 y rows of the plane
+//    x the tile's channels, the next tap's fragment reads in flight during a tap's MFMAs;
 //  * epilogue as the implicit GEMM: bias, BN partial sums (one row per tile), optional
 //    residual + ReLU, bf16 tile transposed through LDS into 16-byte channel stores.
 #include <atomic>
 #include <cstdlib>
 #include <type_traits>
+#include <utility>
 
 #include "bnsum.h"
 #include "common.h"
@@ -50,7 +56,7 @@ constexpr int NSL8 = 2;                    // weight slots
 constexpr int NPL8 = 2;                    // plane slots
 constexpr int RING8 = NPL8 * PLANE8;
 constexpr int ZERO8 = RING8 + NSL8 * BSLOT8;
-constexpr int MAIN8 = ZERO8 + RB8;
+constexpr int MAIN8 = ZERO8 + NC * RB8;        // 8 zero rows, one per class
 constexpr int CROW8 = BN8 * 2 + 16;
 constexpr int EPI8 = PL8 * CROW8 + 7 * 2 * BN8 * 4;   // + partial sums of up to 7 wave rows
 constexpr int LDS8 = MAIN8 > EPI8 ? MAIN8 : EPI8;
@@ -67,76 +73,165 @@ struct L8 {
 };
 
 __device__ __forceinline__ int swz8(int row) { return 3 * ((row >> 3) & 1); }
+// x-walk form, plane image: keyed on the parity of tx ^ ty (row bits 3 and 6), so the two
+// halves of a y-pair fragment (64 rows apart, any y shift) sit on different chunks
+__device__ __forceinline__ int swz8x(int row) { return 3 * (((row >> 3) ^ (row >> 6)) & 1); }
 
-template <int TN, int NFR>
+// ---- x-pair form: wave WM owns plane row ty = WM, fragment q is its x pair (2q, 2q + 1)
+template <int TN>
 struct Fr8 {
   bf16x8 b[TN];
-  bf16x8 a[NFR];
+  bf16x8 a[4];
 };
 
-// fragment f of wave row WM (WR plane rows per wave): plane row ty = WR*WM + (f >> 2),
-// x pair j = f & 3
-template <int WM, int KY, int WR>
-__device__ constexpr bool row_ok(int f) {
-  return WR * WM + (f >> 2) + KY >= 0 && WR * WM + (f >> 2) + KY < S8;
+template <int WM, int KY>
+__device__ constexpr bool row_ok() {
+  return WM + KY >= 0 && WM + KY < S8;
 }
 
 // ao: this lane's row offset + chunk for an even (index 0) / odd (1) x shift; zlane: the
 // lane's zero-row address; lhi: lane is the fragment's second x position
-template <int TN, int WM, int KY, int KX, int WR>
+template <int TN, int WM, int KY, int KX>
 __device__ __forceinline__ void read8(const char* bsl, const char* pl, const uint32_t (&ao)[2],
-                                      const char* zp, bool lhi, Fr8<TN, 4 * WR>& f) {
+                                      const char* zp, bool lhi, Fr8<TN>& f) {
 #pragma unroll
   for (int j = 0; j < TN; ++j)
     f.b[j] = *reinterpret_cast<const bf16x8*>(bsl + (KX + 1) * BTAP8 + j * 16 * RB8);
 #pragma unroll
-  for (int q = 0; q < 4 * WR; ++q) {
-    if (row_ok<WM, KY, WR>(q)) {
-      constexpr int dummy = 0;
-      const int ty = WR * WM + (q >> 2) + KY + dummy, x0 = 2 * (q & 3) + KX;
+  for (int q = 0; q < 4; ++q) {
+    if (row_ok<WM, KY>()) {
+      const int ty = WM + KY, x0 = 2 * q + KX;
       const int base = (ty * S8 + x0) * NC * RB8;       // may be -8 rows: lanes redirected
       const char* p = pl + base + ao[KX & 1];
-      if (KX == -1 && (q & 3) == 0) p = lhi ? p : zp;
-      if (KX == 1 && (q & 3) == 3) p = lhi ? zp : p;
+      if (KX == -1 && q == 0) p = lhi ? p : zp;
+      if (KX == 1 && q == 3) p = lhi ? zp : p;
       f.a[q] = *reinterpret_cast<const bf16x8*>(p);
     }
   }
 }
 
-template <int TN, int WM, int KY, int WR>
-__device__ __forceinline__ void mma8(f32x4 (&acc)[4 * WR][TN], const Fr8<TN, 4 * WR>& f) {
+template <int TN, int WM, int KY>
+__device__ __forceinline__ void mma8(f32x4 (&acc)[4][TN], const Fr8<TN>& f) {
 #pragma unroll
-  for (int q = 0; q < 4 * WR; ++q)
-    if (row_ok<WM, KY, WR>(q)) {
+  for (int q = 0; q < 4; ++q)
+    if (row_ok<WM, KY>()) {
 #pragma unroll
       for (int j = 0; j < TN; ++j)
         acc[q][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f.a[q], f.b[j], acc[q][j], 0, 0, 0);
     }
 }
 
-template <int TN, int WM, int KY, int WR>
-__device__ __forceinline__ void stage8(f32x4 (&acc)[4 * WR][TN], const char* bsl,
-                                       const char* pl, const uint32_t (&ao)[2], const char* zp,
-                                       bool lhi) {
-  Fr8<TN, 4 * WR> f0, f1;
-  read8<TN, WM, KY, -1, WR>(bsl, pl, ao, zp, lhi, f0);
-  read8<TN, WM, KY, 0, WR>(bsl, pl, ao, zp, lhi, f1);
-  mma8<TN, WM, KY, WR>(acc, f0);
-  read8<TN, WM, KY, 1, WR>(bsl, pl, ao, zp, lhi, f0);
-  mma8<TN, WM, KY, WR>(acc, f1);
-  mma8<TN, WM, KY, WR>(acc, f0);
+template <int TN, int WM, int KY>
+__device__ __forceinline__ void stage8(f32x4 (&acc)[4][TN], const char* bsl, const char* pl,
+                                       const uint32_t (&ao)[2], const char* zp, bool lhi) {
+  Fr8<TN> f0, f1;
+  read8<TN, WM, KY, -1>(bsl, pl, ao, zp, lhi, f0);
+  read8<TN, WM, KY, 0>(bsl, pl, ao, zp, lhi, f1);
+  mma8<TN, WM, KY>(acc, f0);
+  read8<TN, WM, KY, 1>(bsl, pl, ao, zp, lhi, f0);
+  mma8<TN, WM, KY>(acc, f1);
+  mma8<TN, WM, KY>(acc, f0);
 }
 
-// TN = 16-column MFMA tiles per wave: 2 (64-channel tiles) or 1 (32 channels, for layers
-// whose 64-channel tiling leaves CUs idle)
+// ---- x-walk form (exact grid): a fragment is two y-neighbouring positions (ty, ty + 1) at
+// one x, x 8 classes, so a kx shift moves whole fragments: the fragment of x at tap kx is the
+// fragment of x + kx at kx = 0.  A wave owns y pair WP at all 8 x (8 accumulator fragments x
+// TN column tiles); per ky row it reads the 8 fragments of the shifted row pair once, uses
+// them for the three kx taps, and leaves out the two (x, kx) that fall off the plane: 22
+// fragment-taps a row on every wave.  Only pair 0 at ky = -1 and pair 3 at ky = +1 have a
+// half in the y padding; that half reads the zero rows.
+// ao: the lane's row + chunk offset for an even (index 0) / odd (1) x + ky; zl: the same in
+// the zero rows; lhi: the lane is in the fragment's second half (ty + 1)
+template <int WP, int KY, int X0, int X1>
+__device__ __forceinline__ void read_ax(const char* pl, const uint32_t (&ao)[2],
+                                        const char* const (&zl)[2], bool lhi,
+                                        bf16x8 (&a)[S8]) {
+#pragma unroll
+  for (int x = X0; x < X1; ++x) {
+    const int k = (x + KY + 2) & 1;
+    const char* p = pl + ((2 * WP + KY) * S8 + x) * NC * RB8 + ao[k];
+    if (WP == 0 && KY == -1) p = lhi ? p : zl[k];
+    if (WP == 3 && KY == 1) p = lhi ? zl[k] : p;
+    a[x] = *reinterpret_cast<const bf16x8*>(p);
+  }
+}
+
+template <int TN>
+__device__ __forceinline__ void read_bx(const char* bsl, int tap, bf16x8 (&b)[TN]) {
+#pragma unroll
+  for (int j = 0; j < TN; ++j)
+    b[j] = *reinterpret_cast<const bf16x8*>(bsl + tap * BTAP8 + j * 16 * RB8);
+}
+
+// one stage as one stream over its 9 taps: row ky + 1's fragments and the weights two taps
+// ahead are read during a tap's MFMAs, one read in each of the first MFMA gaps
+template <int TN, int WP>
+__device__ __forceinline__ void stage8x(f32x4 (&acc)[S8][TN], const char* bsl, const char* pl,
+                                        const uint32_t (&ao)[2], const char* const (&zl)[2],
+                                        bool lhi) {
+  bf16x8 a[2][S8], b[3][TN];
+  read_bx<TN>(bsl, 0, b[0]);
+  read_ax<WP, -1, 0, S8>(pl, ao, zl, lhi, a[0]);
+  read_bx<TN>(bsl, 1, b[1]);
+  __builtin_amdgcn_sched_barrier(0);
+  auto tap = [&](auto tc) __attribute__((always_inline)) {
+    constexpr int T = decltype(tc)::value, R = T / 3, KX = T % 3 - 1;
+    constexpr int X0 = 3 * (KX + 1), X1 = KX == 1 ? S8 : X0 + 3;   // next row's share: 3, 3, 2
+    constexpr int NR = (T + 2 < TPS8 ? TN : 0) + (R < 2 ? X1 - X0 : 0);
+    constexpr int NM = (KX == 0 ? S8 : S8 - 1) * TN;
+    static_assert(NM >= NR, "a read per MFMA gap");
+    if constexpr (T + 2 < TPS8) read_bx<TN>(bsl, T + 2, b[(T + 2) % 3]);
+    if constexpr (R < 2) read_ax<WP, R, X0, X1>(pl, ao, zl, lhi, a[(R + 1) & 1]);
+#pragma unroll
+    for (int x = 0; x < S8; ++x)
+      if (x + KX >= 0 && x + KX < S8) {
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+          acc[x][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[R & 1][x + KX], b[T % 3][j],
+                                                              acc[x][j], 0, 0, 0);
+      }
+#ifndef L8X_NO_INTERLEAVE   // (A/B build: the issue order left to the compiler)
+#pragma unroll
+    for (int k = 0; k < NR; ++k) {
+      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // 1 MFMA
+      __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);   // 1 LDS read
+    }
+    if constexpr (NM > NR) __builtin_amdgcn_sched_group_barrier(0x008, NM - NR, 0);
+#endif
+  };
+  [&]<int... T>(std::integer_sequence<int, T...>) {
+    (tap(std::integral_constant<int, T>{}), ...);
+  }(std::make_integer_sequence<int, TPS8>{});
+}
+
+// The sum of squares of a lane's 16 values in the BN rows, with the roundings of the x-pair
+// form's `cq += v * v` as compiled, which the rows' bits include: in every 16-column tile but
+// a tile's last the products are fused into the adds, fma(v0, v0, v1 * v1) first and
+// fma(vi, vi, q) from there; in the last they are rounded on their own (that tile's sum and
+// square sum run as one packed add).  tests/test_lattice8_xwalk_gpu.py holds the two forms
+// to the same bits.
+__device__ __forceinline__ float sqsum16(const float (&v)[16], bool fused) {
+#pragma clang fp contract(off)
+  float qf = __builtin_fmaf(v[0], v[0], v[1] * v[1]);
+  float qu = v[0] * v[0];
+  qu = qu + v[1] * v[1];
+#pragma unroll
+  for (int i = 2; i < 16; ++i) {
+    qf = __builtin_fmaf(v[i], v[i], qf);
+    qu = qu + v[i] * v[i];
+  }
+  return fused ? qf : qu;
+}
+
+// TN = 16-column MFMA tiles per wave.  x-pair form: 4 (64-channel tiles) or 2 (32 channels,
+// for layers whose 64-channel tiling leaves CUs idle); x-walk form, whose waves split the
+// channels in two: 2 or 1
 // RAG: ragged grids (any D x H x W with ceil(H / 2), ceil(W / 2) <= 8: the reference's
 // 91 x 109 x 91 MNI volumes give 12 x 14 x 12 at layer3), as latticeconv.hip's RAG form:
 // the positions / planes a class lacks are LDS-DMA'd as zeros (buffer resource, offset past
 // its end) and skipped in the epilogue.
-// WR = plane rows per wave: 2 (4 x 2 waves of 128 rows x 16 TN channels) or 1 (8 waves of
-// 64 rows, one y row each, x 16 TN channels: the same tile width at TN doubled, 4 A + TN B
-// fragment reads per tap instead of 8 + TN / 2 ... for the same MFMAs)
-template <int TN, bool RAG, int WR>
+// XW: the x-walk form (exact grid only)
+template <int TN, bool RAG, bool XW = false>
 __global__ __launch_bounds__(NT8) void lattice8_conv_kernel(L8 g, const u16* __restrict__ src,
                                                             const u16* __restrict__ wgt,
                                                             const float* __restrict__ bias,
@@ -153,13 +248,14 @@ __global__ __launch_bounds__(NT8) void lattice8_conv_kernel(L8 g, const u16* __r
   const int t2 = tile / g.nbn;
   const int NZ = RAG ? g.nz : S8;
   const int tz = t2 % NZ, n = t2 / NZ;
-  constexpr int NFR = 4 * WR;                      // A fragments per wave
-  constexpr int NWM = 8 / WR, NWN = WR;            // wave rows x wave columns
+  static_assert(!XW || !RAG, "the x-walk form is the exact grid's");
+  constexpr int NFR = XW ? S8 : 4;                 // A fragments per wave
+  constexpr int NWM = XW ? 4 : 8, NWN = XW ? 2 : 1;   // wave rows x wave columns
   constexpr int BW = 16 * TN * NWN;                // output channels of this tile
   const int n0 = nt * BW;
   constexpr int E = 2 * S8;                          // 16
 
-  if (tid < RB8 / 16)
+  if (tid < (XW ? NC : 1) * RB8 / 16)              // (x-walk form: a zero row per class)
     *reinterpret_cast<u32x4*>(smem + ZERO8 + tid * 16) = u32x4{0u, 0u, 0u, 0u};
 
   // ---- patch DMA: plane slot p <- plane tz - 1 + p, chunk cc; 4 instructions per wave of
@@ -175,7 +271,7 @@ __global__ __launch_bounds__(NT8) void lattice8_conv_kernel(L8 g, const u16* __r
     const int row = (wave * 4 + k) * 16 + lrow;
     const int pos = row >> 3, c = row & 7;
     const int ty = pos >> 3, tx = pos & 7;
-    const int pch = (lane & 3) ^ swz8(row);
+    const int pch = (lane & 3) ^ (XW ? swz8x(row) : swz8(row));
     if constexpr (RAG) {
       const int y = ((c >> 1) & 1) + 2 * ty, x = (c & 1) + 2 * tx;
       pofs[k] = (uint32_t)((((c >> 2) * g.H + y) * g.W + x) * g.Cs + pch * 8) * 2u;
@@ -248,6 +344,15 @@ __global__ __launch_bounds__(NT8) void lattice8_conv_kernel(L8 g, const u16* __r
   ao[0] = lr * RB8 + ((lk ^ swz8(lr)) << 4);
   ao[1] = lr * RB8 + ((lk ^ (3 - swz8(lr))) << 4);   // rows shifted by 8: the other swizzle
   const char* zp = smem + ZERO8 + (lk << 4);
+  const char* zl[2] = {zp, zp};
+  if constexpr (XW) {                               // halves a plane row apart, class rows
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      const uint32_t o = (lr & 7) * RB8 + ((lk ^ (3 * (k ^ (int)lhi))) << 4);
+      ao[k] = (lhi ? S8 * NC * RB8 : 0) + o;
+      zl[k] = smem + ZERO8 + o;
+    }
+  }
   const uint32_t b_lane = (wn * 16 * TN + lr) * RB8 + ((lk ^ swz8(lr)) << 4);
   f32x4 acc[NFR][TN];
 #pragma unroll
@@ -275,9 +380,13 @@ __global__ __launch_bounds__(NT8) void lattice8_conv_kernel(L8 g, const u16* __r
         }
         const char* pl = smem + (e & 1) * PLANE8;
         const char* bs = ring + (e & 1) * BSLOT8 + b_lane;
-        stage8<TN, WM, -1, WR>(acc, bs, pl, ao, zp, lhi);
-        stage8<TN, WM, 0, WR>(acc, bs + 3 * BTAP8, pl, ao, zp, lhi);
-        stage8<TN, WM, 1, WR>(acc, bs + 6 * BTAP8, pl, ao, zp, lhi);
+        if constexpr (XW) {
+          stage8x<TN, WM>(acc, bs, pl, ao, zl, lhi);
+        } else {
+          stage8<TN, WM, -1>(acc, bs, pl, ao, zp, lhi);
+          stage8<TN, WM, 0>(acc, bs + 3 * BTAP8, pl, ao, zp, lhi);
+          stage8<TN, WM, 1>(acc, bs + 6 * BTAP8, pl, ao, zp, lhi);
+        }
       }
   };
   auto dispatch = [&](auto wmc) {
@@ -295,8 +404,9 @@ __global__ __launch_bounds__(NT8) void lattice8_conv_kernel(L8 g, const u16* __r
   }
   __syncthreads();                                  // patch / ring reused by the epilogue
 
-  // ---- epilogue: acc[q][j][e] is tile row (ty*8 + 2*(q&3))*8 + lk*4 + e with
-  // ty = WR*wm + (q >> 2), column wn*16*TN + j*16 + lr
+  // ---- epilogue: acc[q][j][e] is tile row (wm*8 + 2*q)*8 + lk*4 + e, column
+  // wn*16*TN + j*16 + lr; x-walk form: acc[x][j][e] is tile
+  // row ((2*wm + (lk >> 1))*8 + x)*8 + (lk & 1)*4 + e
   // (RAG: -1 for a row outside the grid)
   auto dst_vox = [&](int row) -> int64_t {
     const int pos = row >> 3, c = row & 7;
@@ -317,23 +427,45 @@ __global__ __launch_bounds__(NT8) void lattice8_conv_kernel(L8 g, const u16* __r
 #pragma unroll 1
     for (int b = 0; b < 4 * NFR; ++b) {
       const int q = b >> 2, e = b & 3;
-      const int row = ((WR * wm + (q >> 2)) * S8 + 2 * (q & 3)) * NC + lk * 4 + e;
+      const int row = (wm * S8 + 2 * q) * NC + lk * 4 + e;
       if (dst_vox(row) >= 0) vmask |= 1u << b;
     }
   }
-  float cs[TN], cq[TN];
+  // x-walk form: the lane's sums over even x in cs / cq and over odd x in cso / cqo, each
+  // in the order (x pair, e) of the x-pair form's lanes, whose bits the BN rows keep
+  float cs[TN], cq[TN], cso[TN], cqo[TN];
 #pragma unroll
   for (int j = 0; j < TN; ++j) {
     cs[j] = 0.f;
     cq[j] = 0.f;
+    cso[j] = 0.f;
+    cqo[j] = 0.f;
     const int col = wn * 16 * TN + j * 16 + lr;
     const float bv = bias != nullptr ? bias[n0 + col] : 0.f;
+    if constexpr (XW) {
+      float ve[16], vo[16];
+#pragma unroll
+      for (int x = 0; x < S8; ++x) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int row = ((2 * wm + (lk >> 1)) * S8 + x) * NC + (lk & 1) * 4 + e;
+          const float v = acc[x][j][e] + bv;
+          ctile[row * (CROW8 / 2) + col] = f2bf(v);
+          (x & 1 ? vo : ve)[(x >> 1) * 4 + e] = v;
+          if (x & 1) cso[j] += v;
+          else cs[j] += v;
+        }
+      }
+      const bool fused = wn * TN + j != 2 * TN - 1;
+      cq[j] = sqsum16(ve, fused);
+      cqo[j] = sqsum16(vo, fused);
+      continue;
+    }
 #pragma unroll
     for (int q = 0; q < NFR; ++q) {
-      const int ty = WR * wm + (q >> 2);
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        const int row = (ty * S8 + 2 * (q & 3)) * NC + lk * 4 + e;
+        const int row = (wm * S8 + 2 * q) * NC + lk * 4 + e;
         const float v = acc[q][j][e] + bv;
         ctile[row * (CROW8 / 2) + col] = f2bf(v);
         if ((vmask >> (q * 4 + e)) & 1u) {
@@ -380,6 +512,41 @@ __global__ __launch_bounds__(NT8) void lattice8_conv_kernel(L8 g, const u16* __r
   }
   if (stats != nullptr) {
     float* red = reinterpret_cast<float*>(smem + PL8 * CROW8);
+    if constexpr (XW) {
+      // the partner class half to each, then even + odd: lanes lk = 0 / 2 hold plane rows
+      // 2 wm / 2 wm + 1; rows 1 .. 7 through LDS, added to row 0 in order
+      const int ty = 2 * wm + (lk >> 1);
+#pragma unroll
+      for (int j = 0; j < TN; ++j) {
+        cs[j] += __shfl_xor(cs[j], 16, 64);
+        cso[j] += __shfl_xor(cso[j], 16, 64);
+        cs[j] += cso[j];
+        cq[j] += __shfl_xor(cq[j], 16, 64);
+        cqo[j] += __shfl_xor(cqo[j], 16, 64);
+        cq[j] += cqo[j];
+        const int col = wn * 16 * TN + j * 16 + lr;
+        if (ty > 0 && (lk & 1) == 0) {
+          red[(ty - 1) * 2 * BW + col] = cs[j];
+          red[(ty - 1) * 2 * BW + BW + col] = cq[j];
+        }
+      }
+      __syncthreads();
+      if (wm == 0 && lk == 0) {
+        const int mt = n * NZ + tz;
+#pragma unroll
+        for (int j = 0; j < TN; ++j) {
+          const int col = wn * 16 * TN + j * 16 + lr;
+          float ss = cs[j], qs = cq[j];
+          for (int w = 1; w < S8; ++w) {            // fixed order: deterministic
+            ss += red[(w - 1) * 2 * BW + col];
+            qs += red[(w - 1) * 2 * BW + BW + col];
+          }
+          stats[((int64_t)mt * 2) * g.Nd + n0 + col] = ss;
+          stats[((int64_t)mt * 2 + 1) * g.Nd + n0 + col] = qs;
+        }
+      }
+      return;
+    }
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
       cs[j] += __shfl_xor(cs[j], 16, 64);
@@ -427,13 +594,18 @@ int lattice8_mode() {
   return v;
 }
 
-// MMAD_L8_ROWS: plane rows per wave, 1 (default: 64-row wave tiles at twice the columns,
-// fewer A-fragment reads per MFMA) or 2 (128-row wave tiles)
-int l8_rows() {
-  static const int v = [] {
-    const char* e = getenv("MMAD_L8_ROWS");
-    return e && atoi(e) == 2 ? 2 : 1;
-  }();
+// MMAD_L8_XWALK: the exact grid's kernel form, 1 (default) the x-walk form (y-pair
+// fragments walked along x), 0 the x-pair form the ragged grids run;
+// mmad_set_kernel_variant("lattice8_xwalk", v) overrides it at run time
+std::atomic<int> g_l8_xwalk{-1};
+int l8_xwalk() {
+  int v = g_l8_xwalk.load(std::memory_order_relaxed);
+  if (v < 0) {
+    const char* e = getenv("MMAD_L8_XWALK");
+    int expect = -1;
+    g_l8_xwalk.compare_exchange_strong(expect, e ? (atoi(e) != 0) : 1);
+    v = g_l8_xwalk.load(std::memory_order_relaxed);
+  }
   return v;
 }
 
@@ -444,6 +616,12 @@ namespace mmad_lattice8 {
 int set_mode(int v) {
   const int prev = lattice8_mode();
   if (v >= 0) g_lattice8_mode.store(v, std::memory_order_relaxed);
+  return prev;
+}
+
+int set_xwalk(int v) {
+  const int prev = l8_xwalk();
+  if (v >= 0) g_l8_xwalk.store(v != 0, std::memory_order_relaxed);
   return prev;
 }
 
@@ -488,14 +666,12 @@ int fwd(const mmad_patch::Geo& q, const void* src, const void* wp, const float* 
            hipSuccess;
   };
   static const bool attr =
-      attr1((const void*)lattice8_conv_kernel<2, false, 2>) &&
-      attr1((const void*)lattice8_conv_kernel<1, false, 2>) &&
-      attr1((const void*)lattice8_conv_kernel<2, true, 2>) &&
-      attr1((const void*)lattice8_conv_kernel<1, true, 2>) &&
-      attr1((const void*)lattice8_conv_kernel<4, false, 1>) &&
-      attr1((const void*)lattice8_conv_kernel<2, false, 1>) &&
-      attr1((const void*)lattice8_conv_kernel<4, true, 1>) &&
-      attr1((const void*)lattice8_conv_kernel<2, true, 1>);
+      attr1((const void*)lattice8_conv_kernel<4, false>) &&
+      attr1((const void*)lattice8_conv_kernel<2, false>) &&
+      attr1((const void*)lattice8_conv_kernel<4, true>) &&
+      attr1((const void*)lattice8_conv_kernel<2, true>) &&
+      attr1((const void*)lattice8_conv_kernel<2, false, true>) &&
+      attr1((const void*)lattice8_conv_kernel<1, false, true>);
   if (!attr) return MMAD_EUNSUPPORTED;
   const bool rag = !exact8(q);
   const int nz = planes8(q);
@@ -518,12 +694,11 @@ int fwd(const mmad_patch::Geo& q, const void* src, const void* wp, const float* 
     hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(NT8), LDS8, as_stream(stream), g,
                        (const u16*)src, (const u16*)wp, bias, (u16*)dst, stats);
   };
-  if (l8_rows() == 1) {                             // one plane row per wave
-    if (wide) rag ? go(lattice8_conv_kernel<4, true, 1>) : go(lattice8_conv_kernel<4, false, 1>);
-    else rag ? go(lattice8_conv_kernel<2, true, 1>) : go(lattice8_conv_kernel<2, false, 1>);
-  } else {                                          // two plane rows per wave
-    if (wide) rag ? go(lattice8_conv_kernel<2, true, 2>) : go(lattice8_conv_kernel<2, false, 2>);
-    else rag ? go(lattice8_conv_kernel<1, true, 2>) : go(lattice8_conv_kernel<1, false, 2>);
+  if (!rag && l8_xwalk()) {                         // y pairs walked along x
+    wide ? go(lattice8_conv_kernel<2, false, true>) : go(lattice8_conv_kernel<1, false, true>);
+  } else {                                          // x pairs, one plane row per wave
+    if (wide) rag ? go(lattice8_conv_kernel<4, true>) : go(lattice8_conv_kernel<4, false>);
+    else rag ? go(lattice8_conv_kernel<2, true>) : go(lattice8_conv_kernel<2, false>);
   }
   return launch_status();
 }

@@ -108,6 +108,7 @@ int wgrad(const mmad_patch::Geo& g, const void* x, const void* dy, float* ws, in
 // Residue-class conv for dilation-2 3^3 convs on a 16^3 grid (lattice8.hip, layer3).
 namespace mmad_lattice8 {
 int set_mode(int v);              // MMAD_LATTICE8 at run time; returns the previous mode
+int set_xwalk(int v);             // MMAD_L8_XWALK at run time; returns the previous value
 bool ok(const mmad_patch::Geo& g);
 int64_t tiles(const mmad_patch::Geo& g);
 int fwd(const mmad_patch::Geo& g, const void* src, const void* wp, const float* bias, void* dst,
