@@ -549,6 +549,27 @@ enum { MMAD_PAD_ZEROS = 0, MMAD_PAD_BORDER = 1 };
 int mmad_affine_resample3d(int b, int d, int h, int w, const double* x, const double* theta,
                            const double* gain_bias, int64_t gb_stride, int padding,
                            double* out, void* stream);
+/* Elastic deformation: a control lattice per sample, lattice [b][3][gd][gh][gw] (float64),
+ * component order (x, y, z) = (w, h, d) as theta's rows, values in voxels, every extent in
+ * [2, 12].  Control point i of an axis with G points sits at normalised coordinate
+ * -1 + 2 i / (G - 1): the lattice spans the whole [-1, 1] cube.
+ *
+ * mmad_elastic_draw: every value uniform in +-max of its own axis (x: max_w, y: max_h,
+ * z: max_d), from the same device-resident seed and counter hash as mmad_augment_draw (read
+ * when the kernel runs), keyed by (sample, component, point): a sample's lattice does not
+ * depend on b.  A negative or NaN bound is MMAD_EBADSHAPE. */
+int mmad_elastic_draw(int b, int gd, int gh, int gw, double max_d, double max_h, double max_w,
+                      const uint64_t* seed, double* lattice, void* stream);
+/* mmad_affine_resample3d with the sampling position g = theta (p, 1) + 2 u(p) / size per
+ * component, u(p) the trilinear interpolation of the sample's lattice at lattice coordinate
+ * (p + 1) (G - 1) / 2 per axis (p: the output voxel's normalised centre); from g on the same
+ * arithmetic, so a zero lattice reproduces the affine result bit for bit -- except that there
+ * is no mirroring fast path here.  Same contract: out must not alias x, d * h * w < 2^31,
+ * gain_bias may be NULL. */
+int mmad_deform_resample3d(int b, int d, int h, int w, const double* x, const double* theta,
+                           int gd, int gh, int gw, const double* lattice,
+                           const double* gain_bias, int64_t gb_stride, int padding,
+                           double* out, void* stream);
 
 /* ---- device-resident dataset cache (float64 in and out, compact exact storage) --------
  * Replaces the DataLoader's collate + .to(device) per batch and nibabel's get_fdata

@@ -197,6 +197,9 @@ _SIGS = {
                                  _vp]),
     "mmad_affine_resample3d": (_i32, [_i32, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _i32, _vp,
                                       _vp]),
+    "mmad_elastic_draw": (_i32, [_i32, _i32, _i32, _i32, _f64, _f64, _f64, _vp, _vp, _vp]),
+    "mmad_deform_resample3d": (_i32, [_i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp,
+                                      _vp, _i64, _i32, _vp, _vp]),
     "mmad_cache_stride_bytes": (_i64, [_i32, _i64]),
     "mmad_cache_ws_bytes": (_i64, []),
     "mmad_cache_store": (_i32, [_i32, _i32, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp]),
