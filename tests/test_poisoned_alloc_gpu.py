@@ -1,0 +1,1052 @@
+"""Every op under a poisoned allocator with guard bands (tests/_poison.py).
+
+``run3(fn)`` calls ``fn`` three times: plain, with every ``torch.empty`` / ``torch.empty_like``
+buffer of the package pre-filled with NaN (integers 1), and pre-filled with zero bytes, each
+buffer between two 512-byte margins; the test-made operands sit between NaN margins
+(``guarded``).  It asserts that
+
+  (a) no margin byte changed (a store outside an output, a partial-sum buffer, a workspace);
+  (b) every float result is finite;
+  (c) the three runs agree bit for bit, result by result, the full BN partial-sum tensors
+      included: a result must not depend on what an output or workspace held before the
+      kernel ran, nor on what lies next to an operand;
+  (d) the plain run meets the bar the op's own test applies against its reference.
+
+The shapes are the small ones of the op's own tests (partial tiles, several splits), the
+specialised conv routes are forced at batch 1 and checked through the BN partial-sum row
+count and the profiler's kernel names."""
+import contextlib
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+import multimodal_alzheimer_amd as M
+from multimodal_alzheimer_amd import _lib as L
+from multimodal_alzheimer_amd import augment, device_cache as dc, head_ops, medicalnet, preprocess
+from multimodal_alzheimer_amd import layers as Lyr
+from multimodal_alzheimer_amd import volume_ops as V
+from tests import _golden as G
+from tests import _poison as P
+from tests.test_kernels_gpu import CONV_CASES, _BN, _ref_bn, close, rnd, to_vol
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda"
+CL = torch.channels_last_3d
+BF = torch.bfloat16
+F32 = torch.float32
+DTYPES = [pytest.param(F32, id="f32"), pytest.param(BF, id="bf16")]
+
+
+# ------------------------------------------------------------------------------ the runner
+def run3(fn, bar=None, kernels=()):
+    """fn() plain, under poisoned("A") and under poisoned("B"); asserts (a) - (d) of the module
+    docstring.  ``kernels``: substrings of kernel names the plain run must have launched
+    (checked where the profiler returns any).  Returns the plain run's results."""
+    out = {}
+    if kernels:
+        from tests.test_lattice5_gpu import _kernels_of
+        names = _kernels_of(lambda: out.__setitem__("plain", fn()))
+        for k in kernels if names is not None else ():
+            assert any(k in n for n in names), f"{k} did not run"
+    else:
+        out["plain"] = fn()
+    torch.cuda.synchronize()
+    for fill in ("A", "B"):
+        with P.poisoned(fill) as p:
+            out[fill] = fn()
+            assert p.records, "nothing was allocated through torch.empty"
+            p.check()                                                            # (a)
+    keys = list(out["plain"])
+    for tag, res in out.items():
+        assert list(res) == keys, tag
+        for k, t in res.items():
+            if t.is_floating_point():
+                assert torch.isfinite(t).all(), f"{k}: non-finite in the {tag} run"  # (b)
+    for tag in ("A", "B"):
+        for k in keys:
+            a, b = out["plain"][k], out[tag][k]
+            assert a.shape == b.shape and a.dtype == b.dtype and a.stride() == b.stride(), k
+            if not torch.equal(a, b):                                            # (c)
+                n = int((a != b).sum())
+                raise AssertionError(f"{k}: {n} of {a.numel()} elements differ between the "
+                                     f"plain run and the run under fill {tag}")
+    if bar is not None:
+        bar(out["plain"])                                                        # (d)
+    return out["plain"]
+
+
+@contextlib.contextmanager
+def variants(**modes):
+    """mmad_set_kernel_variant(name, mode) for the block; the previous modes afterwards"""
+    lib = L.load()
+    prev = {}
+    try:
+        for k, v in modes.items():
+            prev[k] = lib.mmad_set_kernel_variant(k.encode(), v)
+            assert prev[k] >= 0, f"unknown kernel variant {k}"
+        yield
+    finally:
+        for k, v in prev.items():
+            lib.mmad_set_kernel_variant(k.encode(), v)
+
+
+def _dev_vol(shape, gen, dtype=BF, normal=False):
+    t = torch.randn(shape, generator=gen, device=DEV) if normal else \
+        torch.rand(shape, generator=gen, device=DEV) * 2 - 1
+    return t.to(dtype).contiguous(memory_format=CL)
+
+
+def _conv_fn(x, w, b, gy, geom, dtype, defer=None, need_dx=True):
+    """forward with BN partial sums + backward of one conv on guarded copies of the operands;
+    ``defer``: None = plain backward, else under deferred_wgrad_reduce(defer) + flush"""
+    s, p, dl = geom
+
+    def fn():
+        xg = P.guarded(x).requires_grad_(need_dx)
+        wg = P.guarded(w).requires_grad_(True)
+        bg = None if b is None else P.guarded(b).requires_grad_(True)
+        y, stats = V.conv3d(xg, wg, bg, (s,) * 3, (p,) * 3, (dl,) * 3, dtype, want_stats=True)
+        g = P.guarded(gy)
+        if defer is None:
+            y.backward(g)
+        else:
+            with V.deferred_wgrad_reduce(defer):
+                y.backward(g)
+                V.flush_wgrad_reduce()
+        torch.cuda.synchronize()
+        res = {"y": y.detach(), "stats": stats, "dw": wg.grad}
+        if b is not None:
+            res["db"] = bg.grad
+        if need_dx:
+            res["dx"] = xg.grad
+        return res
+    return fn
+
+
+# ----------------------------------------------- 3a. convs: the shape table of test_kernels_gpu
+# fp32 runs every conv through the implicit GEMM (the specialised routes are bf16 only):
+# layer3 (dilation 2, ragged), layer4 (dilation 4) and the stride-2 shortcut of odd extents
+IGEMM_F32 = [CONV_CASES[8], CONV_CASES[11], CONV_CASES[12]]
+_CONV_PARAMS = [pytest.param(c, BF, id=f"{i}-ci{c[1]}co{c[5]}k{c[6]}s{c[7]}d{c[9]}-bf16")
+                for i, c in enumerate(CONV_CASES)] + \
+               [pytest.param(c, F32, id=f"{CONV_CASES.index(c)}-ci{c[1]}co{c[5]}k{c[6]}s{c[7]}"
+                                        f"d{c[9]}-f32") for c in IGEMM_F32]
+
+
+@pytest.mark.parametrize("case,dtype", _CONV_PARAMS)
+def test_conv_table(case, dtype):
+    """operands, float64 CPU reference and bars of test_kernels_gpu.test_conv3d_fwd_bwd"""
+    n, ci, d, h, w, co, k, s, p, dl, has_bias = case
+    x = rnd(n, ci, d, h, w, seed=1)
+    wt = rnd(co, ci, k, k, k, seed=2, scale=(3.0 / (ci * k ** 3)) ** 0.5)
+    b = rnd(co, seed=3) if has_bias else None
+    if dtype == BF:
+        x = x.to(BF).double()
+        wt = wt.float().to(BF).double()
+    xr = x.clone().requires_grad_(ci > 1)
+    wr = wt.clone().requires_grad_(True)
+    br = b.clone().requires_grad_(True) if has_bias else None
+    yr = F.conv3d(xr, wr, br, s, p, dl)
+    gy = rnd(*yr.shape, seed=4)
+    if dtype == BF:
+        gy = gy.to(BF).double()
+    yr.backward(gy)
+
+    def bar(r):
+        tol = 2e-5 if dtype == F32 else 1.2e-2
+        stol = 1e-4 if dtype == F32 else 2e-2
+        gtol = 3e-5 if dtype == F32 else 2e-2
+        close(r["y"], yr, tol, "y")
+        yd = yr.detach()
+        close(r["stats"][:, 0].sum(0), yd.sum(dim=(0, 2, 3, 4)), stol, "stats.sum")
+        close(r["stats"][:, 1].sum(0), (yd ** 2).sum(dim=(0, 2, 3, 4)), stol, "stats.sumsq")
+        close(r["dw"], wr.grad, gtol, "dw")
+        if has_bias:
+            close(r["db"], br.grad, gtol, "db")
+        if ci > 1:
+            close(r["dx"], xr.grad, gtol, "dx")
+
+    xd = x.to(DEV, F32) if ci == 1 else to_vol(x, dtype)
+    fn = _conv_fn(xd, wt.float().to(DEV), b.float().to(DEV) if has_bias else None,
+                  to_vol(gy, dtype), (s, p, dl), dtype, need_dx=ci > 1)
+    run3(fn, bar)
+
+
+# -------------------------------------- 3a. the weight-gradient routes of the ResNet-10 step
+def _cols(x, k, s, p, d):
+    """im2col of an (N, C, D, H, W) volume: (N Do Ho Wo, C k^3), columns in weight order"""
+    u = F.pad(x, (p,) * 6)
+    for dim in (2, 3, 4):
+        u = u.unfold(dim, (k - 1) * d + 1, s)
+    u = u[..., ::d, ::d, ::d]                              # N,C,Do,Ho,Wo,k,k,k
+    return u.permute(0, 2, 3, 4, 1, 5, 6, 7).reshape(-1, x.shape[1] * k ** 3)
+
+
+def _gpu_conv_bars(x, w, gy, s, p, dl, check_dx=True):
+    """(d) for the bf16 convs too large for a float64 CPU conv, as im2col + matmul on the
+    device: outputs and input gradients against a plain fp32 conv of the same bf16 operands
+    (2^-7 |ref| + 1e-3 max |ref|, BN totals 1e-3 of the summed magnitudes), the weight
+    gradient against a float64 one (1e-3 |ref| + 1e-4 sum |gY| |X|): the bars of
+    tests/test_lattice5_gpu.py"""
+    from tests.test_fullsize_gpu import _ref_conv
+    from tests.test_lattice5_gpu import _close
+
+    def bar(r):
+        xr = x.detach().float().requires_grad_(True)
+        yr = _ref_conv(xr, w.to(BF).float(), s, p, dl)
+        yr.backward(gy.float())
+        _close(r["y"], yr.detach(), "forward")
+        if check_dx:
+            _close(r["dx"], xr.grad, "input gradient")
+        yd = yr.detach().double()
+        sums = torch.stack((yd.sum(dim=(0, 2, 3, 4)), (yd * yd).sum(dim=(0, 2, 3, 4))))
+        mag = torch.stack((yd.abs().sum(dim=(0, 2, 3, 4)), (yd * yd).sum(dim=(0, 2, 3, 4))))
+        assert ((r["stats"].sum(0).double() - sums).abs() <= 1e-3 * mag + 1e-6).all(), "BN sums"
+        del xr, yr, yd
+        cols = _cols(x.detach().double(), w.shape[2], s, p, dl)
+        gd = gy.double().permute(0, 2, 3, 4, 1).reshape(-1, w.shape[0])
+        wr = (gd.t() @ cols).view(w.shape)
+        wmag = (gd.abs().t() @ cols.abs_()).view(w.shape)
+        err = (r["dw"].double() - wr).abs()
+        assert (err <= 1e-3 * wr.abs() + 1e-4 * wmag).all(), f"dW: max {err.max().item():.3e}"
+    return bar
+
+
+def _route_operands(xs, ws, s, p, dl, seed):
+    from tests.test_wgrad_defer_gpu import _operands
+    x, w = _operands(xs, ws, seed)
+    k = ws[2]
+    oshape = (xs[0], ws[0]) + tuple(V.out_extent(e, k, s, p, dl) for e in xs[2:])
+    gy = _dev_vol(oshape, torch.Generator(device=DEV).manual_seed(5))
+    return x, w, gy
+
+
+def _routes():
+    from tests.test_wgrad_defer_gpu import ROUTES
+    return ROUTES
+
+
+@pytest.mark.parametrize("route", _routes(), ids=[r[0] for r in _routes()])
+def test_wgrad_routes_immediate_and_deferred(route):
+    """each route immediate and with its slab reduction deferred into the batched launch;
+    (d): the deferred dW is the immediate one bit for bit (test_wgrad_defer_gpu's bar) and
+    the immediate results meet the conv bars"""
+    name, xs, ws, s, p, dl = route
+    x, w, gy = _route_operands(xs, ws, s, p, dl, len(name))
+    now = run3(_conv_fn(x, w, None, gy, (s, p, dl), BF), _gpu_conv_bars(x, w, gy, s, p, dl))
+    later = run3(_conv_fn(x, w, None, gy, (s, p, dl), BF, defer=True))
+    for k in now:
+        assert torch.equal(now[k], later[k]), f"{name}: deferred {k} differs"
+
+
+@pytest.mark.parametrize("xs,co", [((1, 64, 6, 16, 40), 64), ((1, 64, 8, 8, 40), 128)],
+                         ids=["ragged", "co128"])
+@pytest.mark.parametrize("defer", [None, True], ids=["immediate", "deferred"])
+def test_pwgrad_w40(xs, co, defer):
+    """the two small cases of test_pwgrad_w40_gpu.py (5 segments of 8 voxels per row)"""
+    ws = (co, xs[1], 3, 3, 3)
+    x, w, gy = _route_operands(xs, ws, 1, 1, 1, xs[2] * 7 + co)
+    run3(_conv_fn(x, w, None, gy, (1, 1, 1), BF, defer=defer),
+         _gpu_conv_bars(x, w, gy, 1, 1, 1), kernels=("pwgrad_kernel<3>",))
+
+
+# ---------------------------------------------- 3a. the specialised routes, forced at batch 1
+# (name, kernel variants, x shape, Co, dilation = padding, BN partial-sum rows of the route,
+#  forward kernel).  lattice_zp needs "lattice" forced as well: the route resolver asks
+#  mmad_lattice::ok for the residue-class geometry first, and that wants 256 tiles unless its
+#  own mode is 2.  Rows: lattice_zp 8 per sample; lattice (d^3 / 32) sub groups x 4 planes;
+#  lattice8 one per sample and z-plane pair (8 exact, ceil(D / 2) ragged); lattice5
+#  (d^3 / 16) x 5; patchz one per 4 x 8 x 8 box.  None of them is the implicit GEMM's count
+#  for its shape (64, 43, 64, 42, 125 and 32 rows).
+FORCED = [
+    ("lattice_zp", {"lattice": 2, "lattice_zp": 2}, (1, 128, 16, 16, 16), 128, 4, 8,
+     "lattice_zp_kernel"),
+    ("lattice", {"lattice": 2, "lattice_zp": 0}, (1, 64, 16, 16, 16), 64, 4, 8,
+     "lattice_conv_kernel"),
+    ("lattice_ragged", {"lattice": 2, "lattice_zp": 0}, (1, 64, 13, 14, 15), 64, 4, 8,
+     "lattice_conv_kernel"),
+    ("lattice8_xpair", {"lattice8": 2, "lattice8_xwalk": 0}, (1, 64, 16, 16, 16), 64, 2, 8,
+     "lattice8_conv_kernel"),
+    ("lattice8_xwalk", {"lattice8": 2, "lattice8_xwalk": 1}, (1, 64, 16, 16, 16), 64, 2, 8,
+     "lattice8_conv_kernel"),
+    # a ragged grid that lattice8's ragged8() accepts (at most 8 x 8 positions per class plane)
+    ("lattice8_ragged_xpair", {"lattice8": 2, "lattice8_xwalk": 0}, (1, 64, 12, 14, 12), 64, 2,
+     6, "lattice8_conv_kernel"),
+    ("lattice8_ragged_xwalk", {"lattice8": 2, "lattice8_xwalk": 1}, (1, 64, 12, 14, 12), 64, 2,
+     6, "lattice8_conv_kernel"),
+    ("lattice5", {"lattice5": 2}, (1, 128, 20, 20, 20), 128, 4, 20, "lattice5_conv_kernel"),
+    ("patchz", {"patchz": 2}, (1, 64, 16, 16, 16), 64, 1, 16, "patchz_conv_kernel"),
+]
+
+
+@pytest.mark.parametrize("name,modes,xs,co,dl,rows,kernel", FORCED, ids=[f[0] for f in FORCED])
+def test_forced_route(name, modes, xs, co, dl, rows, kernel):
+    ws = (co, xs[1], 3, 3, 3)
+    x, w, gy = _route_operands(xs, ws, 1, dl, dl, len(name) * 3 + dl)
+    with variants(**modes):
+        got = L.load().mmad_conv3d_stats_rows(
+            V.conv_desc(xs, ws, (1,) * 3, (dl,) * 3, (dl,) * 3), L.dtype_code(BF))
+        assert got == rows, f"{name}: not routed ({got} BN partial-sum rows, {rows} expected)"
+        r = run3(_conv_fn(x, w, None, gy, (1, dl, dl), BF), _gpu_conv_bars(x, w, gy, 1, dl, dl),
+                 kernels=(kernel,))
+    assert r["stats"].shape[0] == rows
+
+
+# -------------------------------------------------------------- 3a. the fused eval epilogue
+EVAL_CASES = [
+    ("patch", {}, (2, 128, 6, 9, 10), 128, 1),
+    ("lattice_zp", {"lattice": 2, "lattice_zp": 2}, (1, 128, 16, 16, 16), 128, 4),
+    ("igemm", {}, (2, 128, 6, 7, 5), 256, 2),
+]
+
+
+@pytest.mark.parametrize("name,modes,xs,co,dl", EVAL_CASES, ids=[c[0] for c in EVAL_CASES])
+def test_conv_bn_act_eval_residual_relu(name, modes, xs, co, dl):
+    """conv_bn_act_eval (BN folded into the packed weights, residual + ReLU in the conv
+    epilogue) against a float64 CPU conv of the same folded bf16 weights; bar of
+    test_fullsize_gpu.test_layer4_eval_fused_conv_bn_res_relu_full_size: two bf16 roundings,
+    2^-8 (|pre| + |pre + res|) + 1e-3 max |ref|"""
+    torch.manual_seed(21)
+    conv = Lyr.Conv3d(xs[1], co, 3, padding=dl, dilation=dl, bias=False).to(DEV)
+    conv.compute_dtype = BF
+    bn = torch.nn.BatchNorm3d(co).to(DEV)
+    with torch.no_grad():
+        bn.running_mean.uniform_(-0.2, 0.2)
+        bn.running_var.uniform_(0.5, 2.0)
+        bn.weight.uniform_(0.5, 1.5)
+        bn.bias.uniform_(-0.3, 0.3)
+    bn.eval()
+    g = torch.Generator(device=DEV).manual_seed(22)
+    x = _dev_vol(xs, g)
+    res = _dev_vol((xs[0], co) + xs[2:], g)
+
+    def fn():
+        conv._eval_fold = None              # fold and pack again: their buffers are poisoned too
+        with torch.no_grad():
+            y = V.conv_bn_act_eval(P.guarded(x), conv, bn, relu=True, res=P.guarded(res))
+        torch.cuda.synchronize()
+        assert y is not None
+        return {"y": y}
+
+    def bar(r):
+        with torch.no_grad():
+            inv = (1.0 / (bn.running_var.double() + bn.eps).sqrt()).float()
+            scale = bn.weight * inv
+            shift = bn.bias - bn.running_mean * bn.weight * inv
+            wf = (conv.weight * scale.view(-1, 1, 1, 1, 1)).to(BF).double().cpu()
+            pre = F.conv3d(x.double().cpu(), wf, None, 1, dl, dl) + \
+                shift.double().cpu().view(1, -1, 1, 1, 1)
+            rd = res.double().cpu()
+            ref = torch.relu(pre + rd)
+        err = (r["y"].double().cpu() - ref).abs()
+        bound = 2 ** -8 * (pre.abs() + (pre + rd).abs()) + 1e-3 * ref.abs().max()
+        assert (err <= bound).all(), f"max|err| {err.max().item():.3e}"
+        assert (r["y"] == 0).any() and (r["y"] > 0).any()
+
+    with variants(**modes):
+        run3(fn, bar)
+
+
+# ---------------------------------------------------------- 3a. the BN-sum dgrad epilogue
+def test_bnsum_dgrad_epilogue():
+    """bn1 -> relu -> conv2 of a BasicBlock with conv2's dgrad epilogue producing bn1's
+    backward sums (the smallest case of test_bnsum_gpu.py, switched on the same way); (d): that
+    test's bars against the column-sum pass (V.BNSUM off)"""
+    from tests.test_bnsum_gpu import CASES
+    planes, s, dil, n, modes = CASES["layer2_patch"]
+    torch.manual_seed(1)
+    block = medicalnet.BasicBlock(planes, planes, dilation=dil).to(DEV)
+    Lyr.set_compute_dtype(block, BF)
+    block.train()
+    g = torch.Generator(device=DEV).manual_seed(2)
+    x = _dev_vol((n, planes, s, s, s), g, normal=True)
+    gy = _dev_vol((n, planes, s, s, s), g, normal=True)
+    sd = {k: v.clone() for k, v in block.state_dict().items()}
+    calls = []
+
+    def run(bnsum):
+        block.load_state_dict(sd)
+        for q in block.parameters():
+            q.grad = None
+        V.clear_twins()
+        prev, real = V.BNSUM, L.call
+        V.BNSUM = bnsum
+        L.call = lambda name, *a: calls.append(name) or real(name, *a)
+        try:
+            xg = P.guarded(x).requires_grad_(True)
+            out = block(xg)
+            out.backward(P.guarded(gy))
+        finally:
+            L.call = real
+            V.BNSUM = prev
+        torch.cuda.synchronize()
+        res = {"out": out.detach(), "dx": xg.grad}
+        res.update({k: q.grad for k, q in block.named_parameters()})
+        res.update({k: v.clone() for k, v in block.state_dict().items() if "running" in k})
+        return res
+
+    with variants(**modes):
+        ref = run(False)
+        assert "mmad_bn_relu_bwd_reduce" in calls
+        ref = {k: v.clone() for k, v in ref.items()}
+        calls.clear()
+
+        def bar(r):
+            assert "mmad_conv3d_dgrad_bnsum" in calls and "mmad_bn_relu_bwd_reduce" not in calls
+            assert torch.equal(r["out"], ref["out"])
+            for k in ("bn1.weight", "bn1.bias"):
+                e = (r[k].double() - ref[k].double()).abs().max().item()
+                assert e <= 1e-4 * ref[k].double().abs().max().item() + 1e-6, (k, e)
+            for k in r:
+                a = ref[k].double()
+                e = (r[k].double() - a).abs()
+                assert (e <= 2 ** -7 * a.abs() + 2e-3 * a.abs().max()).all(), (k, e.max().item())
+
+        run3(lambda: run(True), bar)
+
+
+# ------------------------------------------------------------------------ 3b. batch norm
+def _bn_case(mode, dtype, shape):
+    """operands, float64 reference and bars of test_kernels_gpu.test_batchnorm_act"""
+    c = shape[1]
+    y0 = rnd(*shape, seed=10, scale=2.0) + 0.5
+    r0 = rnd(*shape, seed=11)
+    if dtype == BF:
+        y0, r0 = y0.to(dtype).double(), r0.to(dtype).double()
+    training = mode != "eval"
+    relu = mode in ("relu", "identity_res", "bn_res")
+    with_res = mode in ("identity_res", "bn_res")
+    bn, rbn = _BN(c, 20), _BN(c, 30)
+    bn.training = rbn.training = training
+    yr = y0.clone().requires_grad_(True)
+    rr = r0.clone().requires_grad_(True)
+    out_r, w1, b1, rm1, rv1 = _ref_bn(yr, bn, training)
+    w2 = None
+    if mode == "identity_res":
+        out_r = out_r + rr
+    if mode == "bn_res":
+        o2, w2, b2, rm2, rv2 = _ref_bn(rr, rbn, training)
+        out_r = out_r + o2
+    if relu:
+        out_r = torch.relu(out_r)
+    g = rnd(*out_r.shape, seed=12)
+    if dtype == BF:
+        g = g.to(dtype).double()
+    out_r.backward(g)
+    yd, rd, gd = to_vol(y0, dtype), to_vol(r0, dtype), to_vol(g, dtype)
+
+    def fn():
+        b1_, b2_ = _BN(c, 20), _BN(c, 30)
+        b1_.training = b2_.training = training
+        yg = P.guarded(yd).requires_grad_(True)
+        rg = P.guarded(rd).requires_grad_(True)
+        out = V.batchnorm_act(yg, b1_, relu=relu, res=rg if with_res else None,
+                              res_bn=b2_ if mode == "bn_res" else None)
+        out.backward(P.guarded(gd))
+        torch.cuda.synchronize()
+        res = {"out": out.detach(), "dy": yg.grad, "dgamma": b1_.weight.grad,
+               "dbeta": b1_.bias.grad, "running_mean": b1_.running_mean,
+               "running_var": b1_.running_var}
+        if with_res:
+            res["dres"] = rg.grad
+        if mode == "bn_res":
+            res.update(dgamma_res=b2_.weight.grad, dbeta_res=b2_.bias.grad,
+                       running_mean_res=b2_.running_mean, running_var_res=b2_.running_var)
+        return res
+
+    def bar(r):
+        tol = 2e-5 if dtype == F32 else 1.5e-2
+        close(r["out"], out_r, tol, "out")
+        close(r["dy"], yr.grad, 5 * tol, "dy")
+        close(r["dgamma"], w1.grad, 5 * tol, "dgamma")
+        close(r["dbeta"], b1.grad, 5 * tol, "dbeta")
+        close(r["running_mean"], rm1, 1e-5, "running_mean")
+        close(r["running_var"], rv1, 1e-5, "running_var")
+        if with_res:
+            close(r["dres"], rr.grad, 5 * tol, "dres")
+        if mode == "bn_res":
+            close(r["dgamma_res"], w2.grad, 5 * tol, "dgamma_res")
+    return fn, bar
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("mode", ["plain", "relu", "identity_res", "bn_res", "eval"])
+def test_batchnorm_act(mode, dtype):
+    run3(*_bn_case(mode, dtype, (2, 64, 5, 6, 7)))
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_batchnorm_pair_c512(dtype):
+    """relu(bn(y) + bn_r(res)) at 512 channels: the one-pass pair kernels"""
+    run3(*_bn_case("bn_res", dtype, (2, 512, 4, 6, 5)))
+
+
+def test_conv_bn_relu_chain_conv_made_partials():
+    """conv (epilogue BN partial sums) -> BN(train, those partials) + ReLU -> conv, fp32:
+    test_kernels_gpu.test_conv_bn_relu_chain at (2, 64, 8, 8, 8)"""
+    shape, c = (2, 64, 8, 8, 8), 64
+    x = rnd(*shape, seed=80)
+    w1 = rnd(c, c, 3, 3, 3, seed=81, scale=(3.0 / (27 * c)) ** 0.5)
+    w2 = rnd(c, c, 3, 3, 3, seed=82, scale=(3.0 / (27 * c)) ** 0.5)
+    xr = x.clone().requires_grad_(True)
+    w1r, w2r = w1.clone().requires_grad_(True), w2.clone().requires_grad_(True)
+    c1 = F.conv3d(xr, w1r, None, 1, 1, 1)
+    a1, gw, gb, rm, rv = _ref_bn(c1, _BN(c, 83), True)
+    out = F.conv3d(torch.relu(a1), w2r, None, 1, 1, 1)
+    gy = rnd(*out.shape, seed=84)
+    out.backward(gy)
+    xd, w1d, w2d, gyd = to_vol(x, F32), w1.float().to(DEV), w2.float().to(DEV), to_vol(gy, F32)
+
+    def fn():
+        bn = _BN(c, 83)
+        xg = P.guarded(xd).requires_grad_(True)
+        w1g, w2g = P.guarded(w1d).requires_grad_(True), P.guarded(w2d).requires_grad_(True)
+        y1, parts = V.conv3d(xg, w1g, None, (1,) * 3, (1,) * 3, (1,) * 3, F32, True)
+        h1 = V.batchnorm_act(y1, bn, parts, relu=True)
+        o = V.conv3d(h1, w2g, None, (1,) * 3, (1,) * 3, (1,) * 3, F32)
+        o.backward(P.guarded(gyd))
+        torch.cuda.synchronize()
+        return {"out": o.detach(), "parts": parts, "dbeta": bn.bias.grad, "dgamma": bn.weight.grad,
+                "dw1": w1g.grad, "dw2": w2g.grad, "dx": xg.grad,
+                "running_mean": bn.running_mean, "running_var": bn.running_var}
+
+    def bar(r):
+        close(r["out"], out, 2e-5, "out")
+        close(r["dbeta"], gb.grad, 1e-4, "dbeta")
+        close(r["dgamma"], gw.grad, 1e-4, "dgamma")
+        close(r["dw1"], w1r.grad, 1e-4, "dw1")
+        close(r["dw2"], w2r.grad, 1e-4, "dw2")
+        close(r["dx"], xr.grad, 1e-4, "dx")
+    run3(fn, bar)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("pool_run", [0, 2], ids=["rows", "zwalk"])
+@pytest.mark.parametrize("shape", [(2, 64, 9, 10, 11), (1, 128, 8, 6, 4)], ids=["odd", "c128"])
+def test_batchnorm_relu_maxpool(shape, pool_run, dtype):
+    """the fused stem tail under both pool kernels; bars of
+    test_kernels_gpu.test_bn_relu_maxpool_fused (bf16 gradients against the unfused chain:
+    rounding before the max moves argmaxes between near-equal values)"""
+    c = shape[1]
+    y0 = rnd(*shape, seed=70, scale=2.0)
+    if dtype == BF:
+        y0 = y0.to(dtype).double()
+    yr = y0.clone().requires_grad_(True)
+    out_r, w_r, b_r, rm_r, rv_r = _ref_bn(yr, _BN(c, 71), True)
+    pr = F.max_pool3d(torch.relu(out_r), 3, 2, 1)
+    g = rnd(*pr.shape, seed=72)
+    if dtype == BF:
+        g = g.to(dtype).double()
+    pr.backward(g)
+    yd, gd = to_vol(y0, dtype), to_vol(g, dtype)
+
+    def fn():
+        bn = _BN(c, 71)
+        yb = P.guarded(yd).requires_grad_(True)
+        pb = V.batchnorm_relu_maxpool(yb, bn, None, 3, 2, 1)
+        pb.backward(P.guarded(gd))
+        torch.cuda.synchronize()
+        return {"out": pb.detach(), "dy": yb.grad, "dgamma": bn.weight.grad,
+                "dbeta": bn.bias.grad, "running_mean": bn.running_mean,
+                "running_var": bn.running_var}
+
+    def bar(r):
+        tol = 2e-5 if dtype == F32 else 1.5e-2
+        bn_a = _BN(c, 71)
+        ya = yd.clone().requires_grad_(True)
+        pa = V.max_pool3d(V.batchnorm_act(ya, bn_a, relu=True), 3, 2, 1)
+        pa.backward(gd)
+        assert torch.equal(pa, r["out"]), "fused forward differs from the unfused chain"
+        close(r["out"], pr, tol, "out")
+        close(r["dy"], ya.grad, tol, "dy fused vs unfused")
+        close(r["dgamma"], bn_a.weight.grad, tol, "dgamma fused vs unfused")
+        close(r["dbeta"], bn_a.bias.grad, tol, "dbeta fused vs unfused")
+        if dtype == F32:
+            close(r["dy"], yr.grad, 5 * tol, "dy")
+            close(r["dgamma"], w_r.grad, 5 * tol, "dgamma")
+            close(r["dbeta"], b_r.grad, 5 * tol, "dbeta")
+        close(r["running_mean"], rm_r, 1e-5, "running_mean")
+        close(r["running_var"], rv_r, 1e-5, "running_var")
+
+    with variants(pool_run=pool_run):
+        run3(fn, bar)
+
+
+# ---------------------------------------------------------------------- 3b. pools and heads
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("k,s,p,shape", [(3, 2, 1, (2, 64, 9, 10, 11)), (2, 2, 0, (2, 16, 9, 8, 7))],
+                         ids=["k3s2p1", "k2s2p0"])
+def test_max_pool3d(k, s, p, shape, dtype):
+    x = torch.relu(rnd(*shape, seed=40)).to(dtype).double()     # exact zeros: ties everywhere
+    xr = x.clone().requires_grad_(True)
+    yr = F.max_pool3d(xr.float(), k, s, p).double()             # torch CPU kernel = the tie rule
+    g = rnd(*yr.shape, seed=41).to(dtype).double()
+    yr.backward(g)
+    xd, gd = to_vol(x, dtype), to_vol(g, dtype)
+
+    def fn():
+        xg = P.guarded(xd).requires_grad_(True)
+        y = V.max_pool3d(xg, k, s, p)
+        y.backward(P.guarded(gd))
+        torch.cuda.synchronize()
+        return {"y": y.detach(), "dx": xg.grad}
+
+    def bar(r):
+        assert torch.equal(r["y"].double().cpu(), yr.detach())
+        close(r["dx"], xr.grad, 1e-6 if dtype == F32 else 1e-2, "dx")
+    run3(fn, bar)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_global_avg_pool(dtype):
+    x = rnd(3, 512, 4, 5, 6, seed=50).to(dtype).double()
+    xr = x.clone().requires_grad_(True)
+    yr = F.adaptive_avg_pool3d(xr, 1)
+    g = rnd(3, 512, 1, 1, 1, seed=51)
+    yr.backward(g)
+    xd, gd = to_vol(x, dtype), g.float().to(DEV)
+
+    def fn():
+        xg = P.guarded(xd).requires_grad_(True)
+        y = V.global_avg_pool(xg)
+        y.backward(P.guarded(gd))
+        torch.cuda.synchronize()
+        return {"y": y.detach(), "dx": xg.grad}
+
+    def bar(r):
+        close(r["y"], yr, 1e-6, "gap")
+        close(r["dx"], xr.grad, 1e-6 if dtype == F32 else 5e-3, "dgap")
+    run3(fn, bar)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("relu", [True, False], ids=["relu", "plain"])
+def test_gap_linear(dtype, relu):
+    """the fused GAP + Linear head on the smallest case of test_gap_linear_gpu.py; (d): bit
+    identical to global_avg_pool -> flatten -> linear, as there"""
+    shape, n_out = (2, 64, 2, 2, 2), 3
+    g = torch.Generator(device=DEV).manual_seed(sum(shape))
+    x = _dev_vol(shape, g, dtype, normal=True)
+    w = torch.randn((n_out, shape[1]), device=DEV, generator=g) * 0.05
+    b = torch.randn(n_out, device=DEV, generator=g) * 0.1
+    gy = torch.randn((shape[0], n_out), device=DEV, generator=g)
+
+    def run(fused):
+        xg, wg, bg = (P.guarded(t).requires_grad_(True) for t in (x, w, b))
+        if fused:
+            y = head_ops.gap_linear(xg, wg, bg, relu=relu)
+        else:
+            y = head_ops.linear(torch.flatten(V.global_avg_pool(xg), 1), wg, bg, relu=relu)
+        y.backward(P.guarded(gy))
+        torch.cuda.synchronize()
+        return {"y": y.detach(), "dx": xg.grad, "dW": wg.grad, "dbias": bg.grad}
+
+    def bar(r):
+        ref = run(False)
+        for k in r:
+            assert torch.equal(r[k], ref[k]), k
+        assert r["y"].abs().sum() > 0
+    run3(lambda: run(True), bar)
+    run3(lambda: run(False))
+
+
+def test_linear_concat_split_relu():
+    """head_ops.linear over concat_features (forward: concat, backward: split) + relu;
+    reference and bars of test_kernels_gpu.test_linear_concat_relu"""
+    x1, x2 = rnd(8, 64, seed=60), rnd(8, 64, seed=61)
+    w, b = rnd(64, 128, seed=62, scale=0.1), rnd(64, seed=63)
+    refs = [t.clone().requires_grad_(True) for t in (x1, x2, w, b)]
+    yr = torch.relu(F.linear(torch.cat(refs[:2], 1), refs[2], refs[3]))
+    g = rnd(8, 64, seed=64)
+    yr.backward(g)
+    dev = [t.float().to(DEV) for t in (x1, x2, w, b)]
+    gd = g.float().to(DEV)
+
+    def fn():
+        gs = [P.guarded(t).requires_grad_(True) for t in dev]
+        cat = head_ops.concat_features(gs[0], gs[1])
+        y = V.relu(head_ops.linear(cat, gs[2], gs[3]))
+        y.backward(P.guarded(gd))
+        torch.cuda.synchronize()
+        return {"cat": cat.detach(), "y": y.detach(), "dx1": gs[0].grad, "dx2": gs[1].grad,
+                "dw": gs[2].grad, "db": gs[3].grad}
+
+    def bar(r):
+        assert torch.equal(r["cat"], torch.cat(dev[:2], 1))
+        close(r["y"], yr, 1e-5, "linear")
+        for a, nm in zip(refs, ("dx1", "dx2", "dw", "db")):
+            close(r[nm], a.grad, 1e-5, nm)
+    run3(fn, bar)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_dropout_fixed_seed(dtype):
+    """mask from a fixed seed; (d): keep rate, scaling and gradient routing as in
+    test_kernels_gpu.test_dropout_keep_rate_scaling_routing (4 sigma of the binomial + 1e-3)"""
+    n, p = 1 << 14, 0.2
+    g = torch.Generator(device=DEV).manual_seed(3)
+    x = (torch.rand(n, device=DEV, generator=g) + 0.5).to(dtype)
+    gy = (torch.rand(n, device=DEV, generator=g) - 0.5).to(dtype)
+    v = _dev_vol((2, 8, 3, 4, 5), g, dtype)
+
+    def fn():
+        torch.manual_seed(17)
+        xg = P.guarded(x).requires_grad_(True)
+        y = head_ops.dropout(xg, p, True)
+        y.backward(P.guarded(gy))
+        yv = head_ops.dropout(P.guarded(v), p, True)
+        torch.cuda.synchronize()
+        return {"y": y.detach(), "dx": xg.grad, "y_vol": yv}
+
+    def bar(r):
+        keep = r["y"] != 0
+        rate = keep.float().mean().item()
+        assert abs(rate - (1 - p)) < 4 * ((p * (1 - p) / n) ** 0.5) + 1e-3
+        sc = 1.0 / (1.0 - p)
+        assert torch.equal(r["y"][keep], (x.float() * sc).to(dtype)[keep])
+        assert not r["dx"][~keep].any()
+        assert torch.equal(r["dx"][keep], (gy.float() * sc).to(dtype)[keep])
+        assert r["y_vol"].is_contiguous(memory_format=CL)
+        kv = r["y_vol"] != 0
+        assert torch.equal(r["y_vol"][kv], (v.float() * sc).to(dtype)[kv])
+    run3(fn, bar)
+
+
+@pytest.mark.parametrize("mode", ["ce", "focal"])
+@pytest.mark.parametrize("fused", [False, True], ids=["loss", "logits_and_loss"])
+def test_losses(mode, fused):
+    """weighted cross entropy and focal loss (gamma 2) on the golden logits, C = 3, through
+    both entry points; bars of test_kernels_gpu.test_losses_vs_golden (1e-12)"""
+    gold = G.load("losses")
+    x0 = torch.tensor(gold["x_C3"], device=DEV)
+    y0 = torch.from_numpy(gold["y_C3"]).to(DEV)
+    wts = torch.tensor(G.W3, dtype=torch.float64, device=DEV)
+    key = "ce_C3" if mode == "ce" else "focal_g2_C3"
+
+    def fn():
+        x = P.guarded(x0).requires_grad_(True)
+        y = P.guarded(y0)
+        res = {}
+        if fused:
+            res["logits64"], loss = head_ops.logits_and_loss(
+                x, y, P.guarded(wts) if mode == "ce" else None, 2.0, 0 if mode == "ce" else 1)
+            res["logits64"] = res["logits64"].detach()
+        elif mode == "ce":
+            loss = head_ops.weighted_cross_entropy(x, y, P.guarded(wts))
+        else:
+            loss = head_ops.focal_loss(x, y, 2)
+        loss.backward()
+        torch.cuda.synchronize()
+        res.update(loss=loss.detach(), dlogits=x.grad)
+        return res
+
+    def bar(r):
+        want = float(gold[key + "_loss"])
+        assert abs(r["loss"].item() - want) <= 1e-12 * max(1, abs(want))
+        close(r["dlogits"], torch.from_numpy(gold[key + "_grad"]), 1e-12, "dlogits")
+        if fused:
+            assert torch.equal(r["logits64"], x0.double())
+    run3(fn, bar)
+
+
+# ------------------------------------------------------------------ 3b. element-wise ops
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_maxout_cat_relu(dtype):
+    """maxout (ties to the first operand), cat_channels (+ its split backward) and relu on
+    volumes: exact against torch, as in test_kernels_gpu"""
+    a0, b0 = rnd(2, 16, 3, 5, 4, seed=45), rnd(2, 16, 3, 5, 4, seed=46)
+    b0[:, :4] = a0[:, :4]
+    c0 = rnd(2, 32, 3, 5, 4, seed=49)
+    ad, bd, cd = to_vol(a0, dtype), to_vol(b0, dtype), to_vol(c0, dtype)
+    g1, g2 = to_vol(rnd(2, 16, 3, 5, 4, seed=47), dtype), to_vol(rnd(2, 48, 3, 5, 4, seed=50), dtype)
+
+    def fn():
+        a, b, c, a2 = (P.guarded(t).requires_grad_(True) for t in (ad, bd, cd, ad))
+        y = V.maxout(a, b)
+        y.backward(P.guarded(g1))
+        z = V.cat_channels(a2, c)
+        z.backward(P.guarded(g2))
+        a3 = P.guarded(ad).requires_grad_(True)
+        r = V.relu(a3)
+        r.backward(P.guarded(g1))
+        torch.cuda.synchronize()
+        return {"max": y.detach(), "da": a.grad, "db": b.grad, "cat": z.detach(),
+                "dcat_a": a2.grad, "dcat_c": c.grad, "relu": r.detach(), "drelu": a3.grad}
+
+    def bar(r):
+        ref, idx = torch.max(torch.stack((ad.cpu(), bd.cpu()), 0), 0)   # torch's CPU tie rule
+        ref, idx = ref.to(DEV), idx.to(DEV)
+        assert torch.equal(r["max"], ref)
+        assert torch.equal(r["da"], torch.where(idx == 0, g1, torch.zeros_like(g1)))
+        assert torch.equal(r["db"], torch.where(idx == 1, g1, torch.zeros_like(g1)))
+        assert torch.equal(r["cat"], torch.cat((ad, cd), 1))
+        assert torch.equal(r["dcat_a"], g2[:, :16]) and torch.equal(r["dcat_c"], g2[:, 16:])
+        assert torch.equal(r["relu"], torch.relu(ad))
+        assert torch.equal(r["drelu"], torch.where(ad > 0, g1, torch.zeros_like(g1)))
+    run3(fn, bar)
+
+
+def test_cast():
+    x = rnd(1000, seed=70).to(DEV)
+    v = to_vol(rnd(2, 8, 3, 4, 5, seed=71), F32)
+
+    def fn():
+        xg = P.guarded(x)
+        y = V.cast(xg, BF)
+        z = V.cast(V.cast(xg, F32), torch.float64)
+        yv = V.cast(P.guarded(v), BF)
+        torch.cuda.synchronize()
+        return {"bf16": y, "f64": z, "vol": yv}
+
+    def bar(r):
+        assert torch.equal(r["bf16"].cpu(), x.cpu().float().to(BF))
+        assert torch.equal(r["f64"].cpu(), x.cpu().float().double())
+        assert torch.equal(r["vol"], v.to(BF)) and r["vol"].is_contiguous(memory_format=CL)
+    run3(fn, bar)
+
+
+# ------------------------------------------------------------- 3b. the input pipeline ops
+def test_device_normalisations():
+    """the three device normalisations at (2, 12, 11, 13) against oracle/preprocess_ref.py:
+    min-max and affine bit-exact, z-score to 1e-12 (the bars of test_preprocess_gpu.py)"""
+    from oracle import preprocess_ref as R
+    from tests._norm_cases import make_case
+    x, m = make_case({"shape": (2, 12, 11, 13), "q": 0.97, "kind": "ints", "seed": 6})
+    xd, md = x.to(DEV), m.to(DEV)
+
+    def fn():
+        xg, mg = P.guarded(xd), P.guarded(md)
+        mm, qs = preprocess.mri_per_scan_minmax(xg, mg, 0.97, return_quantiles=True)
+        z = preprocess.mri_per_scan_zscore(xg, mg)
+        a = preprocess.affine_normalize(xg, 0.5145, 0.5383)
+        torch.cuda.synchronize()
+        return {"minmax": mm, "quantiles": qs, "zscore": z, "affine": a}
+
+    def bar(r):
+        for b in range(x.shape[0]):
+            ref, lo, hi = R.mri_minmax_ref(x[b].clone(), m[b], 0.97)
+            assert (r["quantiles"][b, 0].item(), r["quantiles"][b, 1].item()) == (lo, hi)
+            assert torch.equal(r["minmax"][b].cpu(), ref)
+            zr = R.mri_zscore_ref(x[b].clone(), m[b])
+            assert (r["zscore"][b].cpu() - zr).abs().max().item() <= 1e-12 * zr.abs().max().item()
+        assert torch.equal(r["affine"].cpu(), R.affine_ref(x, 0.5145, 0.5383))
+    run3(fn, bar)
+
+
+def test_augmentation_draw_and_resample():
+    """one draw (affine, intensity, elastic lattice) from a fixed seed, the affine resample and
+    the elastic resample on the smallest case of test_elastic_gpu.py; (d): that file's oracle
+    on the drawn parameters at its bar (1e-12 of max |ref|), the lattice within its bounds"""
+    from tests.test_elastic_gpu import CASES, assert_close, oracle, volume
+    shape, grid = min(CASES, key=lambda c: np.prod(c[0]))
+    vox = (1.5, 0.75, 2.25)
+    cfg = {"elastic_vox": vox, "elastic_grid": grid, "rotate_deg": 10.0, "gain": [0.9, 1.1],
+           "translate_vox": 1.0}
+    x = volume(shape, 31)
+    xd = x.to(DEV)
+
+    def fn():
+        torch.manual_seed(41)
+        xg = P.guarded(xd)
+        theta, intensity, lattice = augment.draw(cfg, shape[0], shape[1:], DEV, nmod=2,
+                                                 return_lattice=True)
+        aff = augment.resample(xg, theta, "zeros", intensity[:, 0])
+        ela = augment.resample(xg, theta, "border", intensity[:, 1], lattice=lattice)
+        torch.cuda.synchronize()
+        return {"theta": theta, "intensity": intensity, "lattice": lattice, "affine": aff,
+                "elastic": ela}
+
+    def bar(r):
+        th, it, lat = r["theta"].cpu(), r["intensity"].cpu(), r["lattice"].cpu()
+        assert lat.shape == (shape[0], 3) + tuple(grid)
+        for axis, bound in enumerate(vox):                  # axis d, h, w <-> component 2, 1, 0
+            assert 0 < lat[:, 2 - axis].abs().max().item() <= bound
+        zero = torch.zeros((shape[0], 3, 2, 2, 2), dtype=torch.float64)
+        assert_close(r["affine"], oracle(x, th, zero, "zeros", it[:, 0]), "affine")
+        assert_close(r["elastic"], oracle(x, th, lat, "border", it[:, 1]), "elastic")
+    run3(fn, bar)
+
+
+def test_device_cache_build_and_fetch():
+    """DeviceVolumeCache of 3 samples at 16^3 (float32 storage, bit mask, tabular rows, labels)
+    built and fetched; (d): the stored samples come back bit for bit"""
+    n, shape = 3, (16, 16, 16)
+    g = torch.Generator().manual_seed(48)
+    x32 = (torch.randn((n,) + shape, dtype=torch.float64, generator=g) * 100.0).float().double()
+    mask = (torch.rand((n,) + shape, generator=g) > 0.4).double()
+    tab = torch.rand((n, dc.TABULAR_COLS), dtype=torch.float64, generator=g)
+    label = torch.arange(n) % 3
+    idx = [2, 0, 2]
+
+    def fn():
+        cache = dc.DeviceVolumeCache.from_tensors(label, mri=x32, mri_mask=mask, tabular=tab,
+                                                  pet1451=x32.flip(0))
+        got = cache.fetch(idx)
+        torch.cuda.synchronize()
+        assert cache.storage == "float32" and not cache.bad_index_seen()
+        return {k: v for k, v in got.items() if torch.is_tensor(v)}
+
+    def bar(r):
+        for k, want in (("mri", x32), ("pet1451", x32.flip(0)), ("mri_mask", mask),
+                        ("tabular", tab)):
+            a = r[k].cpu()
+            assert a.dtype == torch.float64
+            assert torch.equal(a.view(torch.int64), want[idx].view(torch.int64)), k
+        assert torch.equal(r["label"].cpu(), label[idx])
+    run3(fn, bar)
+
+
+# ----------------------------------------------------------------- 3c. whole steps, eager
+def _step_results(m, batch, mode="train"):
+    out = m.general_step({k: P.guarded(v) for k, v in batch.items()}, 0, mode)
+    res = {"logits": out["outputs"].detach(), "loss": out["loss"].detach()}
+    if mode == "train":
+        out["loss"].backward()
+        res.update({"grad/" + k: p.grad for k, p in m.named_parameters() if p.grad is not None})
+        res.update({"buf/" + k: b for k, b in m.named_buffers()})
+    torch.cuda.synchronize()
+    return res
+
+
+def _anat_model(precision):
+    from tests.test_model_parity_gpu import build_product
+    gold = G.load("anat_r10_32_live")
+    m = build_product("anat_r10_32_live")
+    G.load_prng_weights(m, int(gold["seed"]))
+    M.layers.set_compute_dtype(m, precision)
+    return m.to(DEV)
+
+
+def test_anat_resnet10_train_step_fp32():
+    """Anat_CNN ResNet-10 at 2 x 1 x 32^3 (golden case anat_r10_32_live: live gradients),
+    general_step + backward in fp32; (d): test_model_parity_gpu.test_model_matches_reference's
+    bars on that case (logits 1e-4, argmax, loss 1e-4, gradients 1e-2 of the tensor's max or
+    the float64 bar, buffers 2e-3)"""
+    from tests.test_model_parity_gpu import LOGIT_ATOL, _assert_f64_bar, _f64_oracle_grads
+    name = "anat_r10_32_live"
+    gold = G.load(name)
+    batch = {k: v.to(DEV) for k, v in G.batch_of(name, gold).items()}
+
+    def fn():
+        m = _anat_model(F32)
+        m.train()
+        return _step_results(m, batch)
+
+    def bar(r):
+        got = r["logits"].cpu().numpy()
+        assert np.abs(got - gold["train_logits"]).max() <= LOGIT_ATOL
+        assert (got.argmax(1) == gold["train_logits"].argmax(1)).all()
+        want = float(gold["train_loss"])
+        assert abs(r["loss"].item() - want) <= 1e-4 * max(1.0, abs(want))
+        gscale = max(np.abs(gold[k]).max() for k in gold
+                     if k.startswith("grad/") and "/stats/" not in k)
+        checked, f64 = 0, None
+        for key in gold:
+            kind, _, rest = key.partition("/")
+            if kind not in ("grad", "buf"):
+                continue
+            sub, _, pname = rest.partition("/")
+            a = r[f"{kind}/{pname}"].detach().double().cpu().numpy().ravel()
+            ref = gold[key]
+            if sub in ("full", "head"):
+                a = a[: ref.size]
+                scale = max(np.abs(ref).max(), 1e-30)
+                err = np.abs(a - ref).max()
+                tol = (1e-2 * scale + 1e-6 * gscale) if kind == "grad" else 2e-3 * scale
+                if kind == "grad" and err > tol:
+                    f64 = f64 or _f64_oracle_grads(name)[1]
+                    _assert_f64_bar(key, a, ref, f64[pname][: ref.size], gscale,
+                                    r[f"{kind}/{pname}"].shape[0])
+                else:
+                    assert err <= tol, f"{key}: err {err:.3e} (ref max {scale:.3e})"
+            else:
+                got3 = np.array([a.sum(), np.abs(a).sum(), np.sqrt((a * a).sum())])
+                np.testing.assert_allclose(got3[1:], ref[1:], rtol=2e-3, err_msg=key)
+            checked += 1
+        assert checked > 3
+    run3(fn, bar)
+
+
+def test_anat_resnet10_train_step_bf16():
+    """the same step in bf16; (d): test_model_parity_gpu.test_bf16_mode_tracks_fp32's bar
+    (logit drift within 5e-2 of the golden fp32 logits' scale, finite gradients)"""
+    gold = G.load("anat_r10_32_live")
+    batch = {k: v.to(DEV) for k, v in G.batch_of("anat_r10_32_live", gold).items()}
+
+    def fn():
+        m = _anat_model(BF)
+        m.train()
+        return _step_results(m, batch)
+
+    def bar(r):
+        ref = gold["train_logits"]
+        err = np.abs(r["logits"].cpu().numpy() - ref).max()
+        assert err <= 5e-2 * max(1.0, np.abs(ref).max()), f"bf16 drift {err:.3e}"
+        assert sum(k.startswith("grad/") for k in r) > 20
+    run3(fn, bar)
+
+
+def test_anat_resnet10_eval_forward_bf16():
+    """one eval forward in bf16: the fused conv-BN(-residual-ReLU) path; (d):
+    test_model_parity_gpu.test_eval_fused_blocks_match_unfused's bf16 bar against the unfused
+    op sequence (3e-2 of the logits' scale)"""
+    gold = G.load("anat_r10_32_live")
+    batch = {k: v.to(DEV) for k, v in G.batch_of("anat_r10_32_live", gold).items()}
+    calls = []
+    real = V.conv_bn_act_eval
+
+    def spy(*a, **k):
+        y = real(*a, **k)
+        calls.append(y is not None)
+        return y
+
+    def fn():
+        m = _anat_model(BF)
+        m.eval()
+        with torch.no_grad():
+            return _step_results(m, batch, "val")
+
+    def bar(r):
+        assert any(calls), "the fused conv-BN path did not run"
+        m = _anat_model(BF)
+        m.eval()
+        prev = medicalnet.EVAL_FUSED
+        medicalnet.EVAL_FUSED = False
+        try:
+            with torch.no_grad():
+                ref = m.general_step(batch, 0, "val")["outputs"].float()
+        finally:
+            medicalnet.EVAL_FUSED = prev
+        err = (r["logits"].float() - ref).abs().max().item()
+        assert err <= 3e-2 * max(1.0, ref.abs().max().item()), err
+
+    V.conv_bn_act_eval = spy
+    try:
+        run3(fn, bar)
+    finally:
+        V.conv_bn_act_eval = real
+
+
+def test_pet_mri_fusion_train_step_bf16():
+    """the two-backbone PET + MRI fusion (ResNet-10 x 2 + MLP head, the smaller model of
+    test_fusion_configs_gpu.py) at 2 x 32^3, one bf16 train step; (d): that file's bf16 bar
+    against the fp32 HIP path on the same weights (3e-2 on logits and loss, finite gradients)"""
+    from tests.test_fusion_configs_gpu import _batch, _hp, _live, _pair
+    h = _hp("pair")
+    batch = {k: v.to(DEV) for k, v in _batch(2, 32, 72, False).items()}
+
+    def build(precision):
+        m = _pair(dict(h, precision=precision), True)
+        G.load_prng_weights(m, 71)
+        _live(m)
+        return m.to(DEV).train()
+
+    def bar(r):
+        ref = _step_results(build("32"), batch)
+        scale = max(1.0, ref["logits"].abs().max().item())
+        assert (r["logits"] - ref["logits"]).abs().max().item() <= 3e-2 * scale
+        assert abs(r["loss"].item() - ref["loss"].item()) <= 3e-2 * max(1.0, abs(ref["loss"].item()))
+        assert {k for k in r if k.startswith("grad/")} == {k for k in ref if k.startswith("grad/")}
+    run3(lambda: _step_results(build("bf16"), batch), bar)
