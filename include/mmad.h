@@ -616,6 +616,42 @@ int mmad_cache_fetch_rows(int b, int64_t n, int cols, const int64_t* labels, con
                           const int64_t* order, const int64_t* cursor, int64_t order_len,
                           int64_t* out_labels, double* out_tab, int32_t* bad, void* stream);
 
+/* ---- occlusion sensitivity (explain.occlusion) -----------------------------------------
+ * No reference counterpart: the reference has no attribution code.  The three entries feed a
+ * captured eval forward and fold its scores into a map, with no host work between replays.
+ *
+ * Windows of a volume (d, h, w) with patch (pd, ph, pw) and stride (td, th, tw),
+ * 1 <= t_a <= p_a <= s_a: per axis n_a = max(1, ceil((s_a - p_a) / t_a) + 1) windows start
+ * at min(i * t_a, s_a - p_a) (every window is full size, the last one shifted back); window
+ * j = (iz * n_h + iy) * n_w + ix; nwin must equal n_d * n_h * n_w (else MMAD_EBADSHAPE).
+ * Slot i of m * b slots holds sample i % b; at cursor value c (a device int64 read when the
+ * kernel runs) it carries window c + i / b.  vox = d * h * w < 2^31, m * b <= 65535.
+ *
+ * mmad_occlude_windows: src [b][d][h][w] and slots [m * b][d][h][w] of dtype MMAD_F64 or
+ *   MMAD_F32 (contiguous, aligned to the element); fill [b] float64.  For each slot, a voxel
+ *   of window c + i / b gets (dtype)fill[i % b]; a voxel of window c - m + i / b (the window
+ *   the previous replay wrote) that is not in the new one gets the source value; nothing else
+ *   is touched, and a window index outside [0, nwin) selects no voxel.  The two voxel sets are
+ *   disjoint, so overlapping windows do not depend on any order between threads.  16-byte
+ *   vectors where w, pw, both windows' x offsets and both base addresses allow it, single
+ *   elements otherwise.
+ * mmad_occlusion_drop: logits [m * b][c] float64, target [b] int64, base [b] float64 ->
+ *   drops[(c + i / b) * b + i % b] = base[i % b] - score(row i) for window indices inside
+ *   [0, nwin); mode 0: score = logits[target], mode 1: its softmax probability (maximum
+ *   subtracted first, the sum taken over ascending class index).  A target outside [0, c)
+ *   is never used as an index: its drop is NaN.  c <= 4096; one block.
+ * mmad_occlusion_map: drops [nwin][b] float64 -> map [b][d][h][w] float32: each voxel's mean
+ *   of the drops of the windows that contain it, summed in ascending j in float64, divided by
+ *   their count, rounded once.  A gather with a fixed order: launches are bit-identical.     */
+int mmad_occlude_windows(int dtype, int b, int m, int d, int h, int w, int pd, int ph, int pw,
+                         int td, int th, int tw, const void* src, void* slots,
+                         const double* fill, const int64_t* cursor, int64_t nwin, void* stream);
+int mmad_occlusion_drop(int mode, int b, int m, int c, const double* logits,
+                        const int64_t* target, const double* base, const int64_t* cursor,
+                        int64_t nwin, double* drops, void* stream);
+int mmad_occlusion_map(int b, int d, int h, int w, int pd, int ph, int pw, int td, int th,
+                       int tw, const double* drops, int64_t nwin, float* map, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

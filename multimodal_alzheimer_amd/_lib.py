@@ -208,6 +208,9 @@ _SIGS = {
                                                                  _vp]),
     "mmad_cache_fetch_rows": (_i32, [_i32, _i64, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp,
                                      _vp]),
+    "mmad_occlude_windows": (_i32, [_i32] * 12 + [_vp, _vp, _vp, _vp, _i64, _vp]),
+    "mmad_occlusion_drop": (_i32, [_i32] * 4 + [_vp, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "mmad_occlusion_map": (_i32, [_i32] * 10 + [_vp, _i64, _vp, _vp]),
 }
 EXPORTS = tuple(_SIGS)
 

@@ -54,6 +54,10 @@ replays a step that loads its own next batch, with no host work and no copy; the
 counts steps on the host, uploads the next epoch's order between replays.  Under
 ``collectives="staged"`` the fetch belongs to the first graph.  The eager warm-up steps run on
 ``batch`` (default: the feed's first batch, which the first replay then trains on again).
+
+:class:`GraphedEvalForward` is the inference twin: an eval-mode ``general_step(..., "pred")``
+over a static batch with optional captured launches before and after it, no optimizer and no
+backward.  ``explain.occlusion`` replays it hundreds of times per explained batch.
 """
 import os
 
@@ -380,4 +384,77 @@ class GraphedTrainStep:
                 self.finish_events.append((e0, e1))
             self.opt_graph.replay()
         volume_ops._BN_UPDATES[0] += 1     # weights / running stats changed on the device
+        return self.out
+
+
+class GraphedEvalForward:
+    """An eval-mode forward over a static batch, captured once and replayed: no optimizer, no
+    backward.  ``model`` must already be in ``eval()`` mode; everything runs under
+    ``torch.no_grad()``.
+
+    The body is ``before(static)`` (optional: launches that prepare the input buffers from
+    device state, e.g. a device cursor), ``model.general_step(static, 0, "pred")["outputs"]``,
+    then ``after(outputs)`` (optional: launches that consume the logits).  ``warmup`` eager
+    runs of the body on a side stream come first, as for :class:`GraphedTrainStep` -- they fold
+    the eval-mode conv weights (``volume_ops.conv_bn_act_eval``), which the captured launches
+    then read -- so whatever ``before`` / ``after`` advance has moved when the constructor
+    returns: reset it before the first replay.
+
+    ``capture=False`` keeps the same object but issues the body's launches from Python on every
+    call (the eager twin of a replay, launch for launch).
+
+    The captured launches hold the addresses of the folded weights: a call after a parameter or
+    a BN running statistic changed raises ``RuntimeError`` (build a new one)."""
+
+    def __init__(self, model, static, warmup=2, before=None, after=None, capture=True):
+        if model.training:
+            raise ValueError("GraphedEvalForward captures an eval-mode forward: call "
+                             "model.eval() first")
+        self.model, self.static = model, static
+        self.before, self.after = before, after
+        self.graph = None
+        self.out = None
+        if not capture:
+            return
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _ in range(max(1, warmup)):
+                self._body()
+        torch.cuda.current_stream().wait_stream(side)
+        self._state = self._model_state()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, capture_error_mode=_CAPTURE_MODE):
+            self.out = self._body()
+        self.graph = g
+
+    def _body(self):
+        with torch.no_grad():
+            if self.before is not None:
+                self.before(self.static)
+            out = self.model.general_step(self.static, 0, "pred")["outputs"]
+            if self.after is not None:
+                self.after(out)
+        return out
+
+    def _model_state(self):
+        return (volume_ops._BN_UPDATES[0],
+                tuple(t._version for t in list(self.model.parameters()) +
+                      list(self.model.buffers())))
+
+    def __call__(self, batch=None):
+        """Run the body once more; ``batch`` (same keys / shapes) is copied into the static
+        buffers first.  Returns the logits (a graph-owned tensor when captured, overwritten by
+        the next replay)."""
+        if batch is not None:
+            for k, v in batch.items():
+                if torch.is_tensor(v):
+                    self.static[k].copy_(v, non_blocking=True)
+        if self.graph is None:
+            self.out = self._body()
+            return self.out
+        if self._model_state() != self._state:
+            raise RuntimeError("the model changed since this forward was captured (weights or "
+                               "BN statistics): capture a new GraphedEvalForward")
+        self.graph.replay()
         return self.out

@@ -12,6 +12,9 @@
 2. Model: ``explain.saliency(method="gradient")`` on bench.py's ResNet-10 at 8 x 128^3 (bf16)
    against one eager training step of the same model (forward + full backward with weight
    gradients, no optimizer).
+3. ``--occlusion`` (on its own): ``explain.occlusion`` on the same ResNet-10 at 1 x 128^3,
+   patch 16, stride 8 (3375 windows, 422 forwards of 8 rows), ``graph=True`` (the replayed
+   capture) against ``graph=False`` (the same launches from Python), whole calls interleaved.
 
 Prints one JSON line.
 """
@@ -112,6 +115,36 @@ def model_times(rounds, calls, precision):
             "calls": calls, "rounds": rounds, "sides": out}
 
 
+def occlusion_times(rounds, precision, patch, stride, size):
+    """explain.occlusion with the replayed graph against the same launches issued from Python"""
+    from bench import hparams
+    g = torch.Generator(device="cuda").manual_seed(1000)
+    batch = {"mri": torch.rand((1, size, size, size), device="cuda", dtype=torch.float64,
+                               generator=g)}
+    torch.manual_seed(15)
+    m = M.Anat_CNN(hparams(precision)).cuda()
+    w = explain.occlusion_windows((size,) * 3, patch, stride)
+    n_win = explain.window_count(w)
+    sides = {"graph": lambda: explain.occlusion(m, batch, patch=patch, stride=stride,
+                                                score="prob", graph=True),
+             "eager": lambda: explain.occlusion(m, batch, patch=patch, stride=stride,
+                                                score="prob", graph=False)}
+    a, b = sides["graph"](), sides["eager"]()
+    out = interleaved(sides, rounds, 1, warm=1)
+    forwards = explain.replay_count(n_win, 8)
+    for k in out:
+        out[k]["ms_per_forward"] = round(out[k]["median_ms"] / (forwards + 1), 4)
+    out["graph"]["ratio_to_eager"] = round(out["graph"]["median_ms"] / out["eager"]["median_ms"],
+                                           3)
+    return {"workload": f"Anat_CNN ResNet-10, 1 x {size}^3, {precision}, patch {patch}, stride "
+                        f"{stride}, score prob: {n_win} windows, {forwards} forwards of 8 rows "
+                        "(+ base forward; the graph side also pays 2 warm-up forwards and the "
+                        "capture per call)",
+            "rounds": rounds, "bit_identical": bool(torch.equal(a["maps"]["mri"],
+                                                                b["maps"]["mri"])),
+            "sides": out}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=5)
@@ -119,9 +152,18 @@ def main():
     ap.add_argument("--model-calls", type=int, default=5)
     ap.add_argument("--precision", default="bf16")
     ap.add_argument("--skip-model", action="store_true")
+    ap.add_argument("--occlusion", action="store_true",
+                    help="time explain.occlusion graph=True against graph=False only")
+    ap.add_argument("--occ-size", type=int, default=128)
+    ap.add_argument("--occ-patch", type=int, default=16)
+    ap.add_argument("--occ-stride", type=int, default=8)
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_explain.py needs a HIP device: a time is only measured on one")
+    if a.occlusion:
+        print(json.dumps({"occlusion": occlusion_times(a.rounds, a.precision, a.occ_patch,
+                                                       a.occ_stride, a.occ_size)}))
+        return
     res = {"kernel": [kernel_times(s, a.rounds, a.calls) for s in SHAPES]}
     if not a.skip_model:
         res["model"] = model_times(a.rounds, a.model_calls, a.precision)
