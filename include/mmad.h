@@ -57,8 +57,9 @@ typedef struct mmad_conv_desc {
 int mmad_abi_version(void);                 /* == MMAD_ABI_VERSION */
 #define MMAD_ABI_VERSION 1
 const char* mmad_strerror(int status);
-/* Kernel-variant switch (the run-time twin of the MMAD_* environment A/B switches; no
- * reference counterpart): "lattice_zp" = 1 plane-pair residue-class conv (default), 0 the
+/* Kernel-variant switch (no reference counterpart): the run-time side of the switch table in
+ * csrc/switches.hip, listed in full -- environment variables, defaults, values -- under
+ * "Kernel switches" in INTEGRATION.md.  Eight switches have a run-time name: "lattice_zp" = 1 plane-pair residue-class conv (default), 0 the
  * one-plane form, 2 plane-pair at any size; "lattice" / "lattice8" / "lattice5" = 1
  * residue-class convs where their tiles fill the CUs (default), 2 at any size, 0 off;
  * "lattice8_xwalk" = 1 lattice8's x-walk form on the exact 16^3 grid (default), 0 the
@@ -67,9 +68,10 @@ const char* mmad_strerror(int status);
  * values the per-output rows kernel; "patchz" = 1 the persistent z-walking layer1 conv where
  * its work items fill the CUs (default), 2 at any size, 0 the per-box patch conv;
  * "pw_wg3_dedup" = 1 the stride-2 3^3 weight gradient on 16-wide rows with de-duplicated
- * input columns (default), 0 its three-image form.  value < 0 only queries.
- * Returns the previous value, -1 for an unknown name.  Not thread-safe against concurrent
- * launches. */
+ * input columns (default), 0 its three-image form.  value < 0 only queries (a negative value
+ * that the switch's environment variable gave is put back by set(name, previous) all the
+ * same).  Returns the previous value, -1 for an unknown or null name; the other switches are
+ * environment-only.  Not thread-safe against concurrent launches. */
 int mmad_set_kernel_variant(const char* name, int value);
 
 /* ---- 3D convolution as MFMA implicit GEMM --------------------------------------

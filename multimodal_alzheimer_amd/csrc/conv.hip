@@ -32,13 +32,13 @@
 //  * XCD-aware tile order: each XCD walks a contiguous range of (m, n) tiles, n fastest;
 //  * epilogue: bias, BN partial sums (sum, sum of squares per channel) from the fp32
 //    accumulators, bf16 tile transposed through LDS into 16-byte channel-vector stores.
-#include <cstring>
 
 #include "common.h"
 #include "reduce.h"
 #include "patchconv.h"
 #include "pointwise.h"
 #include "stem.h"
+#include "switches.h"
 
 namespace {
 
@@ -918,17 +918,13 @@ __global__ __launch_bounds__(256) void wgrad_reduce_batch_kernel(ReduceBatch b) 
 // r03tz: layer1 16.4 / 16.2 -> 10.6 / 10.3 us, layer2.0.conv1 13.9 -> 11.5)
 mmad_reduce::Job plan_reduce_t(const float* ws, float* dw, int splits, int Nd, int K, int Cs,
                               int taps) {
-  static const bool tz_on = [] {
-    const char* e = getenv("MMAD_REDUCE_TZ");
-    return e == nullptr || atoi(e) != 0;
-  }();
   mmad_reduce::Job j{};
   j.ws = ws; j.dw = dw; j.splits = splits; j.nd = Nd; j.k = K; j.cs = Cs; j.taps = taps;
   const int64_t blocks = (int64_t)cdiv(Cs, 64) * Nd;
   const int ct = std::min(64, Cs);
   j.gx = (int)cdiv(Cs, 64);
   j.gy = Nd;
-  if (tz_on && blocks < 256 && taps <= 32 && ct % 4 == 0) {
+  if (sw(SW_REDUCE_TZ) && blocks < 256 && taps <= 32 && ct % 4 == 0) {
     int gz = (int)std::min<int64_t>(taps, cdiv(256, blocks));
     int tper = (int)cdiv(taps, gz);
     while (tper * (ct / 4) > 256) ++gz, tper = (int)cdiv(taps, gz);
@@ -1326,9 +1322,8 @@ struct WSplit { int bmw, splits, m_per_split; };
 // 158 -> 161 triples/s, r04q), so used from M = 49152 on.  MMAD_WGRAD_BIG: 0 never, 1
 // wherever the tile fits, unset the M rule.
 int wgrad_big(const Geom& g, int dtype) {
-  static const int v = [] { const char* e = getenv("MMAD_WGRAD_BIG"); return e ? atoi(e) : -1; }();
   if (dtype != MMAD_BF16 || g.Nd % 256 || g.K < 256 * 8) return 0;
-  if (v >= 0) return v;
+  if (sw(SW_WGRAD_BIG) >= 0) return sw(SW_WGRAD_BIG);
   return g.M >= 49152 ? 1 : 0;
 }
 
@@ -1359,10 +1354,10 @@ WSplit wgrad_split(const Geom& g, int dtype) {
     const double cost = (double)cdiv(tiles * nsp, slots) * stages * c + nsp * slab_mb * r;
     if (cost < best * 0.999) { best = cost; want = sp; }
   }
-  static const int force = [] { const char* e = getenv("MMAD_WGRAD_SPLITS"); return e ? atoi(e) : 0; }();
+  const int force = sw(SW_WGRAD_SPLITS);
   if (force > 0) want = std::min<int64_t>(force, max_split);
   // 1x1x1 convs (the shortcuts): MMAD_WGRAD_1X1_SPLITS overrides the model's count (A/B)
-  static const int force1 = [] { const char* e = getenv("MMAD_WGRAD_1X1_SPLITS"); return e ? atoi(e) : 0; }();
+  const int force1 = sw(SW_WGRAD_1X1_SPLITS);
   if (force1 > 0 && g.taps == 1) want = std::min<int64_t>(force1, max_split);
   s.m_per_split = (int)(cdiv(cdiv(g.M, want), WBK) * WBK);
   s.splits = (int)cdiv(g.M, s.m_per_split);
@@ -1393,21 +1388,12 @@ int launch_igemm_bm(const Geom& g, int64_t m_max, int classes, const void* src, 
 }
 
 // experiment switch for the large-tile configurations (bf16, >= 256 output channels)
-int big_cfg() {
-  static const int v = [] { const char* e = getenv("MMAD_IGEMM_BIG"); return e ? atoi(e) : 0; }();
-  return v;
-}
-int big_min_k() {
-  static const int v = [] { const char* e = getenv("MMAD_IGEMM_BIG_MINK"); return e ? atoi(e) : 1024; }();
-  return v;
-}
+int big_cfg() { return sw(SW_IGEMM_BIG); }
+int big_min_k() { return sw(SW_IGEMM_BIG_MINK); }
 // fewest 256 x 256 tiles for the default big-tile rule: 200, so config 5's 20^3 layer3
 // (64000 x 256, 250 tiles: 6 CUs idle) takes them too -- config-5 step 160.1 -> 165.8
 // triples/s (r04s); MMAD_IGEMM_BIG_MINBLK overrides (256: one tile per CU at least)
-int big_min_blocks() {
-  static const int v = [] { const char* e = getenv("MMAD_IGEMM_BIG_MINBLK"); return e ? atoi(e) : 200; }();
-  return v;
-}
+int big_min_blocks() { return sw(SW_IGEMM_BIG_MINBLK); }
 // ring depth of the default (4-wave) tiles: 3 (two stages of LDS-DMA in flight, still two
 // blocks per CU at 64 x 128 tiles) for strided forward convs with taps (those the stride-2
 // sub-patch kernel does not take: fp32, ragged grids), 2 elsewhere.  Measured in the
@@ -1415,8 +1401,7 @@ int big_min_blocks() {
 // every stride-1 launch and the parity-class dgrads were slower at 3 (e.g. 57.9 -> 71.6
 // us).  MMAD_IGEMM_NST=2 / 3 forces one depth everywhere (A/B).
 int igemm_nst(const Geom& g, int mode) {
-  static const int v = [] { const char* e = getenv("MMAD_IGEMM_NST"); return e ? atoi(e) : 0; }();
-  if (v) return v;
+  if (sw(SW_IGEMM_NST)) return sw(SW_IGEMM_NST);
   return mode == FWD && g.taps > 1 && (g.sd > 1 || g.sh > 1 || g.sw > 1) ? 3 : 2;
 }
 int big_cfg_for(const Geom& g, int dtype, int64_t m_max, int classes) {
@@ -1441,10 +1426,7 @@ static bool al16(const void* a, const void* b, const void* c) {
 }
 
 // MMAD_STEM=0 routes the MedicalNet stem through the generic implicit GEMM (A/B switch)
-bool stem_kernel_on() {
-  static const bool v = [] { const char* e = getenv("MMAD_STEM"); return !e || atoi(e) != 0; }();
-  return v;
-}
+bool stem_kernel_on() { return sw(SW_STEM); }
 // rows per M tile of a forward launch (= rows of the BN partial-sum buffer per tile)
 int fwd_tile_rows(const Geom& g, int dtype) {
   const int cfg = big_cfg_for(g, dtype, g.M, 1);
@@ -1505,10 +1487,7 @@ int run_igemm(const Geom& g, int dtype, int64_t m_max, int classes, const void* 
 }
 
 // MMAD_WGRAD_XCD=0 keeps launch-order block placement (A/B switch)
-int wgrad_xcd() {
-  static const int v = [] { const char* e = getenv("MMAD_WGRAD_XCD"); return e ? atoi(e) : 1; }();
-  return v;
-}
+int wgrad_xcd() { return sw(SW_WGRAD_XCD); }
 
 template <typename T, int BMW, int WBK, int NST, int WBNT, int WGM, int WGN, bool XFIX>
 int launch_wgrad_x(const Geom& g, const WSplit& sp, const void* x, const void* dy, float* ws,
@@ -1540,10 +1519,7 @@ int launch_wgrad_k(const Geom& g, const WSplit& sp, const void* x, const void* d
 // ring depth of the 1x1x1 (shortcut) weight gradients: 3 (two stages in flight; measured r03zf
 // layer4 / 3 / 2 downsample wgrad 26.2 / 13.1 / 11.4 -> 26.0 / 12.1 / 10.1 us), or 2
 // (MMAD_WGRAD_1X1_NST=2, the depth of every other wgrad)
-int wgrad_1x1_nst() {
-  static const int v = [] { const char* e = getenv("MMAD_WGRAD_1X1_NST"); return e ? atoi(e) : 3; }();
-  return v;
-}
+int wgrad_1x1_nst() { return sw(SW_WGRAD_1X1_NST); }
 
 template <typename T, int BMW>
 int launch_wgrad(const Geom& g, const WSplit& sp, const void* x, const void* dy, float* ws,
@@ -1643,20 +1619,9 @@ Route dgrad_fwd_route(const mmad_conv_desc* d, int dtype, Epi epi, Geom* gf) {
 // =====================================================================================
 extern "C" {
 
-// the run-time overrides of the switches the routes above (and the pooling / pointwise
-// kernels) read; returns the previous mode, -1 for an unknown name
-int mmad_set_kernel_variant(const char* name, int value) {
-  if (name == nullptr) return -1;
-  if (std::strcmp(name, "lattice_zp") == 0) return mmad_lattice_zp::set_mode(value);
-  if (std::strcmp(name, "lattice") == 0) return mmad_lattice::set_mode(value);
-  if (std::strcmp(name, "lattice8") == 0) return mmad_lattice8::set_mode(value);
-  if (std::strcmp(name, "lattice8_xwalk") == 0) return mmad_lattice8::set_xwalk(value);
-  if (std::strcmp(name, "lattice5") == 0) return mmad_lattice5::set_mode(value);
-  if (std::strcmp(name, "pool_run") == 0) return mmad_pool::set_run_mode(value);
-  if (std::strcmp(name, "patchz") == 0) return mmad_patchz::set_mode(value);
-  if (std::strcmp(name, "pw_wg3_dedup") == 0) return mmad_pw::set_wg3_dedup(value);
-  return -1;
-}
+// the run-time overrides of the switches (switches.h) the routes above and the pooling /
+// pointwise kernels read; returns the previous value, -1 for an unknown name
+int mmad_set_kernel_variant(const char* name, int value) { return sw_set(name, value); }
 
 int64_t mmad_conv_packed_elems(const mmad_conv_desc* d, int dtype, int for_dgrad) {
   if (!desc_ok(d)) return -1;

@@ -27,12 +27,11 @@
 //    and then tz = 4, the others one interior plane each, the pair blocks dispatched first
 //    on every XCD (each XCD holds whole sub groups, so their input planes share one L2).
 #include <algorithm>
-#include <atomic>
-#include <cstdlib>
 #include <utility>
 
 #include "common.h"
 #include "patchconv.h"
+#include "switches.h"
 
 namespace {
 
@@ -781,27 +780,11 @@ __global__ __launch_bounds__(NTHR) void lattice5_wgrad_kernel(LW5 g, const u16* 
 
 // MMAD_LATTICE5: 1 (default) where the blocks fill the CUs, 2 at any size, 0 off;
 // mmad_set_kernel_variant("lattice5", v) overrides it at run time
-std::atomic<int> g_mode{-1};
-int mode() {
-  int v = g_mode.load(std::memory_order_relaxed);
-  if (v < 0) {
-    const char* e = getenv("MMAD_LATTICE5");
-    int expect = -1;
-    g_mode.compare_exchange_strong(expect, e ? atoi(e) : 1);
-    v = g_mode.load(std::memory_order_relaxed);
-  }
-  return v;
-}
+int mode() { return sw(SW_LATTICE5); }
 
 }  // namespace
 
 namespace mmad_lattice5 {
-
-int set_mode(int v) {
-  const int prev = mode();
-  if (v >= 0) g_mode.store(v, std::memory_order_relaxed);
-  return prev;
-}
 
 static int64_t blocks(const mmad_patch::Geo& q) {
   return (int64_t)q.nb * (q.dd * q.dd * q.dd / NS) * 4 * (q.Nd / BW);

@@ -24,14 +24,13 @@
 //    x the tile's channels, the next tap's fragment reads in flight during a tap's MFMAs;
 //  * epilogue as the implicit GEMM: bias, BN partial sums (one row per tile), optional
 //    residual + ReLU, bf16 tile transposed through LDS into 16-byte channel stores.
-#include <atomic>
-#include <cstdlib>
 #include <type_traits>
 #include <utility>
 
 #include "bnsum.h"
 #include "common.h"
 #include "patchconv.h"
+#include "switches.h"
 
 namespace {
 
@@ -582,48 +581,16 @@ __global__ __launch_bounds__(NT8) void lattice8_conv_kernel(L8 g, const u16* __r
 
 // MMAD_LATTICE8: 1 (default) where the tiles fill the CUs, 2 at any size, 0 off;
 // mmad_set_kernel_variant("lattice8", v) overrides it at run time
-std::atomic<int> g_lattice8_mode{-1};
-int lattice8_mode() {
-  int v = g_lattice8_mode.load(std::memory_order_relaxed);
-  if (v < 0) {
-    const char* e = getenv("MMAD_LATTICE8");
-    int expect = -1;
-    g_lattice8_mode.compare_exchange_strong(expect, e ? atoi(e) : 1);
-    v = g_lattice8_mode.load(std::memory_order_relaxed);
-  }
-  return v;
-}
+int lattice8_mode() { return sw(SW_LATTICE8); }
 
 // MMAD_L8_XWALK: the exact grid's kernel form, 1 (default) the x-walk form (y-pair
 // fragments walked along x), 0 the x-pair form the ragged grids run;
 // mmad_set_kernel_variant("lattice8_xwalk", v) overrides it at run time
-std::atomic<int> g_l8_xwalk{-1};
-int l8_xwalk() {
-  int v = g_l8_xwalk.load(std::memory_order_relaxed);
-  if (v < 0) {
-    const char* e = getenv("MMAD_L8_XWALK");
-    int expect = -1;
-    g_l8_xwalk.compare_exchange_strong(expect, e ? (atoi(e) != 0) : 1);
-    v = g_l8_xwalk.load(std::memory_order_relaxed);
-  }
-  return v;
-}
+int l8_xwalk() { return sw(SW_L8_XWALK); }
 
 }  // namespace
 
 namespace mmad_lattice8 {
-
-int set_mode(int v) {
-  const int prev = lattice8_mode();
-  if (v >= 0) g_lattice8_mode.store(v, std::memory_order_relaxed);
-  return prev;
-}
-
-int set_xwalk(int v) {
-  const int prev = l8_xwalk();
-  if (v >= 0) g_l8_xwalk.store(v != 0, std::memory_order_relaxed);
-  return prev;
-}
 
 static bool exact8(const mmad_patch::Geo& q) {
   constexpr int E = 2 * S8;
@@ -632,11 +599,7 @@ static bool exact8(const mmad_patch::Geo& q) {
 // ragged grids (MMAD_LATTICE_RAGGED, default on): same extents in and out, at most 8 x 8
 // positions per class plane, one sample's bytes addressable by a 32-bit buffer offset
 static bool ragged8(const mmad_patch::Geo& q) {
-  static const int mode = [] {
-    const char* e = getenv("MMAD_LATTICE_RAGGED");
-    return e ? atoi(e) : 1;
-  }();
-  return mode > 0 && !exact8(q) && q.Ds == q.Dd && q.Hs == q.Hd && q.Ws == q.Wd &&
+  return sw(SW_LATTICE_RAGGED) > 0 && !exact8(q) && q.Ds == q.Dd && q.Hs == q.Hd && q.Ws == q.Wd &&
          (q.Hs + 1) / 2 <= S8 && (q.Ws + 1) / 2 <= S8 &&
          (int64_t)q.Ds * q.Hs * q.Ws * q.Cs * 2 < (int64_t(1) << 31);
 }

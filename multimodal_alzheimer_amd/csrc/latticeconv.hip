@@ -34,12 +34,11 @@
 //    channel-vector stores; tiles walk the XCDs in contiguous ranges (the 4 channel tiles
 //    and neighbouring planes of one sub group share an L2).
 #include <algorithm>
-#include <atomic>
-#include <cstdlib>
 #include <type_traits>
 
 #include "common.h"
 #include "patchconv.h"
+#include "switches.h"
 
 namespace {
 
@@ -745,27 +744,11 @@ __global__ __launch_bounds__(NTHR) void lattice_wgrad_kernel(LWG g, const u16* _
 
 // MMAD_LATTICE: 1 (default) where the tiles fill the CUs, 2 at any size, 0 off;
 // mmad_set_kernel_variant("lattice", v) overrides it at run time
-std::atomic<int> g_lattice_mode{-1};
-int lattice_mode() {
-  int v = g_lattice_mode.load(std::memory_order_relaxed);
-  if (v < 0) {
-    const char* e = getenv("MMAD_LATTICE");
-    int expect = -1;
-    g_lattice_mode.compare_exchange_strong(expect, e ? atoi(e) : 1);
-    v = g_lattice_mode.load(std::memory_order_relaxed);
-  }
-  return v;
-}
+int lattice_mode() { return sw(SW_LATTICE); }
 
 }  // namespace
 
 namespace mmad_lattice {
-
-int set_mode(int v) {
-  const int prev = lattice_mode();
-  if (v >= 0) g_lattice_mode.store(v, std::memory_order_relaxed);
-  return prev;
-}
 
 // a 4d^3 grid (every class a full 4^3 sub-lattice) or, with MMAD_LATTICE_RAGGED (default
 // on), a ragged one: same extents in and out, up to 4 x 4 positions per class plane
@@ -773,13 +756,7 @@ static bool exact(const mmad_patch::Geo& q) {
   const int E = S * q.dd;
   return q.Ds == E && q.Hs == E && q.Ws == E && q.Dd == E && q.Hd == E && q.Wd == E;
 }
-static int ragged_mode() {
-  static const int v = [] {
-    const char* e = getenv("MMAD_LATTICE_RAGGED");
-    return e ? atoi(e) : 1;
-  }();
-  return v;
-}
+static int ragged_mode() { return sw(SW_LATTICE_RAGGED); }
 static bool ragged(const mmad_patch::Geo& q) {
   const int d = q.dd;
   return !exact(q) && q.Ds == q.Dd && q.Hs == q.Hd && q.Ws == q.Wd &&
@@ -827,13 +804,7 @@ int wgrad_splits(const mmad_patch::Geo& q) {
 // At 2 waves per SIMD the per-stage fragment reads and barrier are not hidden, so this
 // kernel is only ~2 % ahead of wgrad_kernel (4 blocks of 4 waves per CU) in the step:
 // 4.25-4.30 vs 4.32 ms (MI355X, batch 8, interleaved A/B); l4c2 380 + 20 us (isolated)
-int lattice_wgrad_mode() {
-  static const int v = [] {
-    const char* e = getenv("MMAD_LATTICE_WGRAD");
-    return e ? atoi(e) : 1;
-  }();
-  return v;
-}
+int lattice_wgrad_mode() { return sw(SW_LATTICE_WGRAD); }
 
 bool wgrad_ok(const mmad_patch::Geo& q) {
   if (lattice_mode() <= 0 || lattice_wgrad_mode() <= 0) return false;
@@ -904,11 +875,7 @@ int fwd(const mmad_patch::Geo& q, const void* src, const void* wp, const float* 
   g.nchunk = q.Cs / KC;
   g.res = reinterpret_cast<const u16*>(q.res);
   g.relu = q.relu;
-  static const int prio = [] {
-    const char* e = getenv("MMAD_SETPRIO");
-    return e ? atoi(e) : 0;
-  }();
-  g.prio = prio;
+  g.prio = sw(SW_SETPRIO);
   g.D = q.Ds; g.H = q.Hs; g.W = q.Ws;
   g.nz = planes(q);
   const int64_t nblk = (int64_t)g.ngroups * g.nz * g.nbn;

@@ -31,14 +31,13 @@
 //    stream in 3 to 9 stages ahead;
 //  * padding taps are skipped per fragment at compile time (wave diagonal, plane pair and
 //    tap are template constants in the main loop), as in latticeconv.hip.
-#include <atomic>
-#include <cstdlib>
 #include <type_traits>
 #include <utility>
 
 #include "bnsum.h"
 #include "common.h"
 #include "patchconv.h"
+#include "switches.h"
 
 namespace {
 
@@ -521,28 +520,11 @@ __global__ __launch_bounds__(NTHR) void lattice_zp_kernel(ZG g, const u16* __res
 // MMAD_LATTICE_ZP: 1 (default) plane-pair kernel where it fills the CUs, 0 the one-plane
 // latticeconv.hip kernel, 2 plane-pair at any size; mmad_set_kernel_variant("lattice_zp", v)
 // overrides it at run time (tests compare both forms in one process)
-std::atomic<int> g_zp_mode{-1};
-int zp_mode() {
-  int v = g_zp_mode.load(std::memory_order_relaxed);
-  if (v < 0) {
-    const char* e = getenv("MMAD_LATTICE_ZP");
-    v = e ? atoi(e) : 1;
-    int expect = -1;
-    g_zp_mode.compare_exchange_strong(expect, v);
-    v = g_zp_mode.load(std::memory_order_relaxed);
-  }
-  return v;
-}
+int zp_mode() { return sw(SW_LATTICE_ZP); }
 
 }  // namespace
 
 namespace mmad_lattice_zp {
-
-int set_mode(int v) {
-  const int prev = zp_mode();
-  if (v >= 0) g_zp_mode.store(v, std::memory_order_relaxed);
-  return prev;
-}
 
 // the route resolver (conv.hip) checks the residue-class geometry with mmad_lattice::ok; on
 // top of it this form needs d = 4 (16^3 grids, 64 classes per sample) and enough tiles to
@@ -584,8 +566,7 @@ int fwd(const mmad_patch::Geo& q, const void* src, const void* wp, const float* 
   if (g.bny != nullptr && (stats != nullptr || g.res != nullptr || g.relu || bias != nullptr))
     return MMAD_EUNSUPPORTED;                       // (one epilogue at a time)
   const int64_t nblk = mmad_lattice_zp::tiles(q) * g.nbn;
-  static const int xcd2 = [] { const char* e = getenv("MMAD_ZP_XCD2"); return e ? atoi(e) : 1; }();
-  g.xcd2 = xcd2 && g.nbn == 4 && (nblk / 4) % 4 == 0 && nblk % 8 == 0 ? 1 : 0;
+  g.xcd2 = sw(SW_ZP_XCD2) && g.nbn == 4 && (nblk / 4) % 4 == 0 && nblk % 8 == 0 ? 1 : 0;
   auto go = [&](auto kern, int lds) {
     hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(NTHR), lds, as_stream(stream), g,
                        (const u16*)src, (const u16*)wp, bias, (u16*)dst, stats);

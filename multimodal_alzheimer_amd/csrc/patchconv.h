@@ -38,7 +38,6 @@ int fwd(const Geo& g, const void* src, const void* wp, const float* bias, void* 
 // Persistent z-walking form of the patch conv for 64-channel inputs on grids of 4 x 8 x 8
 // boxes (patchz.hip, layer1): ahead of mmad_patch where both are ok().  No BN-sum epilogue.
 namespace mmad_patchz {
-int set_mode(int v);              // MMAD_PATCHZ at run time; returns the previous mode
 bool ok(const mmad_patch::Geo& g);
 int64_t tiles(const mmad_patch::Geo& g);
 int fwd(const mmad_patch::Geo& g, const void* src, const void* wp, const float* bias, void* dst,
@@ -49,7 +48,6 @@ int fwd(const mmad_patch::Geo& g, const void* src, const void* wp, const float* 
 // geometry record, packed weights and partial-sum layout as the patch kernel.  No BN-sum
 // epilogue.
 namespace mmad_lattice {
-int set_mode(int v);              // MMAD_LATTICE at run time; returns the previous mode
 // fill_tiles: M tiles of the launch that would run g (tiles(g), or mmad_lattice_zp's where
 // that form applies) for the fill-the-CUs rule of mode 1
 bool ok(const mmad_patch::Geo& g, int64_t fill_tiles);
@@ -82,7 +80,6 @@ int dgrad(const mmad_conv_desc* d, const void* dy, const void* wpt, void* dx, vo
 // subs per tile, one wave per SIMD; ahead of mmad_lattice where both are ok() (its ok() adds
 // to mmad_lattice::ok, which checks the residue-class geometry).
 namespace mmad_lattice_zp {
-int set_mode(int v);              // MMAD_LATTICE_ZP at run time; returns the previous mode
 bool ok(const mmad_patch::Geo& g);
 int64_t tiles(const mmad_patch::Geo& g);
 int fwd(const mmad_patch::Geo& g, const void* src, const void* wp, const float* bias, void* dst,
@@ -92,7 +89,6 @@ int fwd(const mmad_patch::Geo& g, const void* src, const void* wp, const float* 
 // Residue-class conv on 5d^3 grids (lattice5.hip: config 5's 20^3 layer4, 5^3 sub-lattices),
 // first among the residue-class kernels.  No BN-sum epilogue.
 namespace mmad_lattice5 {
-int set_mode(int v);              // MMAD_LATTICE5 at run time; returns the previous mode
 bool ok(const mmad_patch::Geo& g);
 int64_t tiles(const mmad_patch::Geo& g);
 int fwd(const mmad_patch::Geo& g, const void* src, const void* wp, const float* bias, void* dst,
@@ -107,8 +103,6 @@ int wgrad(const mmad_patch::Geo& g, const void* x, const void* dy, float* ws, in
 
 // Residue-class conv for dilation-2 3^3 convs on a 16^3 grid (lattice8.hip, layer3).
 namespace mmad_lattice8 {
-int set_mode(int v);              // MMAD_LATTICE8 at run time; returns the previous mode
-int set_xwalk(int v);             // MMAD_L8_XWALK at run time; returns the previous value
 bool ok(const mmad_patch::Geo& g);
 int64_t tiles(const mmad_patch::Geo& g);
 int fwd(const mmad_patch::Geo& g, const void* src, const void* wp, const float* bias, void* dst,
@@ -123,8 +117,3 @@ int64_t workspace(const mmad_patch::Geo& g);
 int wgrad(const mmad_patch::Geo& g, const void* x, const void* dy, float* ws, int* splits,
           void* stream);
 }  // namespace mmad_pwgrad
-
-namespace mmad_pool {
-// MMAD_POOL_RUN run-time override (mmad_set_kernel_variant("pool_run", v)); returns the old mode
-int set_run_mode(int v);
-}  // namespace mmad_pool

@@ -27,11 +27,11 @@
 //  * epilogue as the implicit GEMM: bias, BN partial sums (one row per tile), bf16 tile
 //    transposed through LDS into 16-byte channel-vector stores.
 #include <algorithm>
-#include <cstdlib>
 
 #include "bnsum.h"
 #include "common.h"
 #include "patchconv.h"
+#include "switches.h"
 
 namespace {
 
@@ -343,20 +343,12 @@ __global__ __launch_bounds__(WGM * WGN * 64) void patch_conv_kernel(PG g, const 
   }
 }
 
-int patch_mode() {
-  static const int v = [] { const char* e = getenv("MMAD_PATCH"); return e ? atoi(e) : 1; }();
-  return v;
-}
-
 // 64-channel N tiles only: the 128-wide variant (128 x 64 wave tiles) spills with the
 // fully unrolled tap loop; wider layers run one block per 64-channel slice of the same box
 int bn_for(const mmad_patch::Geo&) { return 64; }
 
 // output-box depth: 2 (two 4-wave blocks per CU) unless MMAD_PATCH_TZ4=1 (4: one 8-wave block)
-int tz_for(const mmad_patch::Geo&) {
-  static const int v = [] { const char* e = getenv("MMAD_PATCH_TZ4"); return e && atoi(e) ? 4 : 2; }();
-  return v;
-}
+int tz_for(const mmad_patch::Geo&) { return sw(SW_PATCH_TZ4) ? 4 : 2; }
 
 PG make_pg(const mmad_patch::Geo& q, int TZ) {
   PG g{};
@@ -407,7 +399,7 @@ int launch(const PG& g, const void* src, const void* wp, const float* bias, void
 namespace mmad_patch {
 
 bool ok(const Geo& q) {
-  const int mode = patch_mode();
+  const int mode = sw(SW_PATCH);
   if (mode <= 0) return false;
   if (q.Cs % 64 || q.Nd % 64 || q.Kpad < q.KD * q.KH * q.KW * q.Cs) return false;
   if (mode == 1 && (q.Cs > 128 || q.Nd > 128)) return false;   // narrow layers only

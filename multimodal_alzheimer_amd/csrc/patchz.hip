@@ -31,13 +31,12 @@
 // Same per-element K order as patchconv.hip (tap-major, channels ascending in 32-wide
 // halves), so the conv outputs are bit-identical to it; only the BN partial sums are grouped
 // into different rows (one per 4x8x8 box instead of per 2x8x8 box).
-#include <atomic>
-#include <cstdlib>
 #include <type_traits>
 #include <utility>
 
 #include "common.h"
 #include "patchconv.h"
+#include "switches.h"
 
 namespace {
 
@@ -437,18 +436,6 @@ __global__ __launch_bounds__(NTHR) void patchz_conv_kernel(PZ g, const u16* __re
   box(g.tps - 1, sb, std::false_type{}, std::true_type{});
 }
 
-std::atomic<int> g_patchz_mode{-1};
-int patchz_mode() {
-  int v = g_patchz_mode.load(std::memory_order_relaxed);
-  if (v < 0) {
-    const char* e = getenv("MMAD_PATCHZ");
-    int expect = -1;
-    g_patchz_mode.compare_exchange_strong(expect, e ? atoi(e) : 1);
-    v = g_patchz_mode.load(std::memory_order_relaxed);
-  }
-  return v;
-}
-
 // z segments per column: the fewest that give every CU a work item, each >= 2 boxes
 int segments(const mmad_patch::Geo& q) {
   const int64_t cols = (int64_t)q.nb * (q.Hd / 8) * (q.Wd / 8) * (q.Nd / 64);
@@ -462,14 +449,8 @@ int segments(const mmad_patch::Geo& q) {
 
 namespace mmad_patchz {
 
-int set_mode(int v) {
-  const int prev = patchz_mode();
-  if (v >= 0) g_patchz_mode.store(v, std::memory_order_relaxed);
-  return prev;
-}
-
 bool ok(const mmad_patch::Geo& q) {
-  if (patchz_mode() <= 0) return false;
+  if (sw(SW_PATCHZ) <= 0) return false;
   if (q.Cs != 64 || q.Nd % 64 || q.Kpad < 27 * 64) return false;
   if (q.KD != 3 || q.KH != 3 || q.KW != 3 || q.dd != 1 || q.dh != 1 || q.dw != 1) return false;
   if (q.pd != 1 || q.ph != 1 || q.pw != 1) return false;
@@ -478,7 +459,7 @@ bool ok(const mmad_patch::Geo& q) {
   const int s = segments(q);
   if (q.Dd / 4 / s < 2) return false;           // nothing to walk
   const int64_t cols = (int64_t)q.nb * (q.Hd / 8) * (q.Wd / 8) * (q.Nd / 64);
-  if (patchz_mode() == 1 && cols * s < 256) return false;   // fewer items than CUs
+  if (sw(SW_PATCHZ) == 1 && cols * s < 256) return false;   // fewer items than CUs
   // per-sample offsets in 32 bits (plane DMA lane offsets, epilogue)
   return (int64_t)q.Ds * q.Hs * q.Ws * 64 < (int64_t(1) << 31) &&
          (int64_t)q.nb * q.Dd * q.Hd * q.Wd * q.Nd < (int64_t(1) << 40);

@@ -18,11 +18,10 @@
 // W[co][ci] with the forward-packed weights [co][ci] as the B rows, N tiles of 256 columns
 // in blockIdx.y, and the BN partial sums of the fp32 accumulators written per 128-row tile
 // (the implicit GEMM ran this K = 128 / 256 GEMM latency-bound: 31.4 / 17.6 us).
-#include <atomic>
-#include <cstdlib>
 
 #include "common.h"
 #include "pointwise.h"
+#include "switches.h"
 
 namespace {
 
@@ -232,13 +231,7 @@ __global__ __launch_bounds__(NTHR) void pw_dgrad_kernel(int K, const u16* __rest
   }
 }
 
-bool pw_on() {
-  static const bool v = [] {
-    const char* e = getenv("MMAD_PW_GEMM");
-    return e == nullptr || atoi(e) != 0;
-  }();
-  return v;
-}
+bool pw_on() { return sw(SW_PW_GEMM); }
 
 // ---- weight gradient (round 5) ------------------------------------------------------
 //   dW[co][ci] = sum_m dY[m][co] * X[src(m)][ci]      (src(m) = m, or s2_src for stride 2)
@@ -564,25 +557,9 @@ __global__ __launch_bounds__(WG_NTHR, 1) void pw_wgrad_kernel(
 
 // MMAD_PW_WG3_DEDUP=0 keeps the three gathered X images per stage for 16-wide rows (A/B);
 // mmad_set_kernel_variant("pw_wg3_dedup", v) overrides it at run time
-std::atomic<int> g_wg3_dedup{-1};
-bool wg3_dedup() {
-  int v = g_wg3_dedup.load(std::memory_order_relaxed);
-  if (v < 0) {
-    const char* e = getenv("MMAD_PW_WG3_DEDUP");
-    int expect = -1;
-    g_wg3_dedup.compare_exchange_strong(expect, e == nullptr || atoi(e) != 0 ? 1 : 0);
-    v = g_wg3_dedup.load(std::memory_order_relaxed);
-  }
-  return v != 0;
-}
+bool wg3_dedup() { return sw(SW_PW_WG3_DEDUP); }
 
-bool pw_wgrad_on() {
-  static const bool v = [] {
-    const char* e = getenv("MMAD_PW_WGRAD");
-    return e == nullptr || atoi(e) != 0;
-  }();
-  return v;
-}
+bool pw_wgrad_on() { return sw(SW_PW_WGRAD); }
 
 }  // namespace
 
@@ -684,12 +661,6 @@ int64_t wg_tiles(const mmad_conv_desc* d) {
   return wg3_geom(d) ? 9 * t : t;
 }
 }  // namespace
-
-int set_wg3_dedup(int v) {
-  const int prev = wg3_dedup() ? 1 : 0;
-  if (v >= 0) g_wg3_dedup.store(v ? 1 : 0, std::memory_order_relaxed);
-  return prev;
-}
 
 bool wgrad_ok(const mmad_conv_desc* d, int dtype) {
   if (!pw_on() || !pw_wgrad_on() || dtype != MMAD_BF16) return false;

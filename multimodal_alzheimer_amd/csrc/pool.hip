@@ -11,11 +11,9 @@
 // torch's CPU kernel; the window index is kept as one byte per output so the backward is
 // a deterministic gather (no atomics) that adds the contributions of the overlapping
 // windows in output order, as torch's CPU backward does.
-#include <atomic>
-#include <cstdlib>
 
 #include "common.h"
-#include "patchconv.h"
+#include "switches.h"
 
 namespace {
 
@@ -772,27 +770,14 @@ __global__ __launch_bounds__(256, POOL_ZW_WAVES) void bnpool3s2_fwd_zwalk_kernel
 }
 
 // MMAD_POOL_ROWS=0 keeps the grid-stride fused pool kernels (A/B switch)
-bool rows_on() {
-  static const bool v = [] { const char* e = getenv("MMAD_POOL_ROWS"); return !e || atoi(e) != 0; }();
-  return v;
-}
+bool rows_on() { return sw(SW_POOL_ROWS); }
 
 // MMAD_POOL_RUN: 2 (default) the z-walking bnpool3s2_fwd_zwalk_kernel for the stem pool (k 3,
 // s 2, p 1, bf16), any other value the per-output rows kernel; mmad_set_kernel_variant(
 // "pool_run", v).  (A column-carrying form -- each thread walking a run of outputs along x --
 // measured 124.5 us against the rows kernel's 110.8 at config 2, r03e: its 2 waves per SIMD
 // did not keep enough loads in flight; removed.)
-std::atomic<int> g_pool_run{-1};
-int pool_run_mode() {
-  int v = g_pool_run.load(std::memory_order_relaxed);
-  if (v < 0) {
-    const char* e = getenv("MMAD_POOL_RUN");
-    int expect = -1;
-    g_pool_run.compare_exchange_strong(expect, e ? atoi(e) : 2);
-    v = g_pool_run.load(std::memory_order_relaxed);
-  }
-  return v;
-}
+int pool_run_mode() { return sw(SW_POOL_RUN); }
 
 unsigned grid_of(int64_t n) {
   return (unsigned)std::max<int64_t>(1, std::min<int64_t>(cdiv(n, 256), 256 * 32));
@@ -1067,11 +1052,3 @@ int mmad_gap_bwd_compact(int dtype, int n, int64_t s, int c, const float* dy, vo
 }
 
 }  // extern "C"
-
-namespace mmad_pool {
-int set_run_mode(int v) {
-  const int prev = pool_run_mode();
-  if (v >= 0) g_pool_run.store(v, std::memory_order_relaxed);
-  return prev;
-}
-}  // namespace mmad_pool

@@ -25,6 +25,7 @@
 //    wgrad_reduce_t_kernel.
 #include "common.h"
 #include "patchconv.h"
+#include "switches.h"
 
 namespace {
 
@@ -383,30 +384,12 @@ __global__ __launch_bounds__(PW_NTHR) void pwgrad_kernel(PWG g, const u16* __res
 
 // MMAD_PWGRAD=0 routes these convs back to the row-gather wgrad_kernel (A/B switch);
 // MMAD_PWGRAD_LAT=0 keeps layer3's dilation-2 convs there
-bool pw_on() {
-  static const bool v = [] {
-    const char* e = getenv("MMAD_PWGRAD");
-    return e == nullptr || atoi(e) != 0;
-  }();
-  return v;
-}
-bool lat_on() {
-  static const bool v = [] {
-    const char* e = getenv("MMAD_PWGRAD_LAT");
-    return e == nullptr || atoi(e) != 0;
-  }();
-  return v;
-}
+bool pw_on() { return sw(SW_PWGRAD); }
+bool lat_on() { return sw(SW_PWGRAD_LAT); }
 
 // MMAD_PWGRAD_W16=0 keeps the 16-wide stride-1 convs on the row-gather wgrad_kernel
 // (measured r03w16: layer2.0.conv2 wgrad 40.0 + 13.4 us reduce -> 29.9 + 10.6)
-bool w16_on() {
-  static const bool v = [] {
-    const char* e = getenv("MMAD_PWGRAD_W16");
-    return e == nullptr || atoi(e) != 0;
-  }();
-  return v;
-}
+bool w16_on() { return sw(SW_PWGRAD_W16); }
 // the 16-wide form: dense 3^3, padding 1, stride 1 on volumes 16 voxels wide and high
 bool w16_geo(const mmad_patch::Geo& q) {
   return q.KD == 3 && q.KH == 3 && q.KW == 3 && q.dd == 1 && q.dh == 1 && q.dw == 1 &&
@@ -414,13 +397,7 @@ bool w16_geo(const mmad_patch::Geo& q) {
          q.Wd == 16 && q.Hd == 16 && q.Dd >= 4;
 }
 // MMAD_PWGRAD_W40=0 keeps the 40-wide convs on the row-gather wgrad_kernel (A/B switch)
-bool w40_on() {
-  static const bool v = [] {
-    const char* e = getenv("MMAD_PWGRAD_W40");
-    return e == nullptr || atoi(e) != 0;
-  }();
-  return v;
-}
+bool w40_on() { return sw(SW_PWGRAD_W40); }
 // the 40-wide form: dense 3^3, padding 1, stride 1 on volumes 40 voxels wide, H % 8 == 0
 bool w40_geo(const mmad_patch::Geo& q) {
   return q.KD == 3 && q.KH == 3 && q.KW == 3 && q.dd == 1 && q.dh == 1 && q.dw == 1 &&
@@ -438,11 +415,7 @@ bool lat_geo(const mmad_patch::Geo& q) {
 // blocks over whole sub-lattices (MMAD_PWGRAD_LAT_NG=1 keeps one group per block; r03ng:
 // layer3.0.conv2 wgrad 90.5 + 20.0 us reduce -> 84.5 + 11.5)
 int lat_ng(const mmad_patch::Geo& q) {
-  static const int force1 = [] {
-    const char* e = getenv("MMAD_PWGRAD_LAT_NG");
-    return e != nullptr && atoi(e) == 1;
-  }();
-  if (!lat_geo(q) || force1) return 1;
+  if (!lat_geo(q) || sw(SW_PWGRAD_LAT_NG) == 1) return 1;
   return (int64_t)q.nb * (q.Cs / PW_KC) * (q.Nd / 64) >= 256 ? 2 : 1;
 }
 

@@ -27,11 +27,11 @@
 //  * epilogue as the implicit GEMM: bias, BN partial sums (one row per tile), optional
 //    residual + ReLU (eval-mode folded BN), bf16 tile transposed through LDS into 16-byte
 //    channel-vector stores.
-#include <cstdlib>
 #include <utility>
 
 #include "common.h"
 #include "patchconv.h"
+#include "switches.h"
 
 namespace {
 
@@ -564,11 +564,6 @@ __global__ __launch_bounds__(NTHR) void s2dgrad_kernel(S2D g, const u16* __restr
   }(std::make_integer_sequence<int, NSTAGE>{});
 }
 
-int s2_mode() {
-  static const int v = [] { const char* e = getenv("MMAD_S2CONV"); return e ? atoi(e) : 1; }();
-  return v;
-}
-
 template <int BN>
 int launch(const S2G& g, int64_t nblk, const void* src, const void* wp, const float* bias,
            void* dst, float* stats, hipStream_t st) {
@@ -586,7 +581,7 @@ int launch(const S2G& g, int64_t nblk, const void* src, const void* wp, const fl
 namespace mmad_s2 {
 
 bool ok(const mmad_patch::Geo& q, int sd, int sh, int sw) {
-  if (s2_mode() <= 0) return false;
+  if (::sw(SW_S2CONV) <= 0) return false;
   if (sd != 2 || sh != 2 || sw != 2) return false;
   if (q.Cs != 64 || q.Nd % 64 || q.Kpad != 27 * 64) return false;
   if (q.KD != 3 || q.KH != 3 || q.KW != 3 || q.pd != 1 || q.ph != 1 || q.pw != 1) return false;
@@ -621,7 +616,7 @@ int fwd(const mmad_patch::Geo& q, int sd, int sh, int sw, const void* src, const
 }
 
 bool dgrad_ok(const mmad_conv_desc* d) {
-  if (s2_mode() <= 0 || d == nullptr) return false;
+  if (sw(SW_S2CONV) <= 0 || d == nullptr) return false;
   if (d->sd != 2 || d->sh != 2 || d->sw != 2 || d->ci != 64 || d->co != 128) return false;
   if (d->kd != 3 || d->kh != 3 || d->kw != 3 || d->pd != 1 || d->ph != 1 || d->pw != 1) return false;
   if (d->dd != 1 || d->dh != 1 || d->dw != 1) return false;

@@ -20,6 +20,7 @@
 
 #include "common.h"
 #include "stem.h"
+#include "switches.h"
 
 namespace {
 
@@ -1022,22 +1023,10 @@ __global__ __launch_bounds__(512) void stem_wgrad2_kernel(StemG g, const TI* __r
 }
 
 // MMAD_STEM_WG2=0 keeps the first stem weight-gradient kernel (A/B switch)
-bool wg2_on() {
-  static const bool on = [] {
-    const char* e = getenv("MMAD_STEM_WG2");
-    return e == nullptr || atoi(e) != 0;
-  }();
-  return on;
-}
+bool wg2_on() { return sw(SW_STEM_WG2); }
 
 // MMAD_STEM_QUAD=0 keeps the y-pair forward kernel (A/B switch)
-bool quad_on() {
-  static const bool on = [] {
-    const char* e = getenv("MMAD_STEM_QUAD");
-    return e == nullptr || atoi(e) != 0;
-  }();
-  return on;
-}
+bool quad_on() { return sw(SW_STEM_QUAD); }
 
 bool geom_for(const mmad_conv_desc* d, StemG& g, int& blocks, size_t& lds, bool quad = false) {
   if (d->ci != 1 || d->co != CO || d->kd != 7 || d->kh != 7 || d->kw > 8) return false;

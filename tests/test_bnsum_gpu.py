@@ -17,6 +17,7 @@ from multimodal_alzheimer_amd import _lib as L
 from multimodal_alzheimer_amd import layers as Lyr
 from multimodal_alzheimer_amd import medicalnet
 from multimodal_alzheimer_amd import volume_ops as V
+from tests._variants import variants
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -57,10 +58,8 @@ def _run(block, x, gy, bnsum, calls):
 
 @pytest.mark.parametrize("name", list(CASES))
 def test_fused_bn_sums_match_column_sum_pass(name):
-    planes, s, dil, n, variants = CASES[name]
-    lib = L.load()
-    prev = {k: lib.mmad_set_kernel_variant(k.encode(), v) for k, v in variants.items()}
-    try:
+    planes, s, dil, n, modes = CASES[name]
+    with variants(**modes):
         torch.manual_seed(1)
         block = medicalnet.BasicBlock(planes, planes, dilation=dil).to(DEV)
         Lyr.set_compute_dtype(block, torch.bfloat16)
@@ -75,9 +74,6 @@ def test_fused_bn_sums_match_column_sum_pass(name):
         o_ref, dx_ref, g_ref = _run(block, x, gy, False, c_ref)
         block.load_state_dict(sd)
         o_new, dx_new, g_new = _run(block, x, gy, True, c_new)
-    finally:
-        for k, v in prev.items():
-            lib.mmad_set_kernel_variant(k.encode(), v)
     assert "mmad_conv3d_dgrad_bnsum" in c_new and "mmad_bn_relu_bwd_reduce" not in c_new
     assert "mmad_bn_relu_bwd_reduce" in c_ref
     assert torch.equal(o_new, o_ref)
@@ -97,10 +93,9 @@ def test_fused_bn_sums_match_column_sum_pass(name):
 def test_bnsum_partial_rows_vs_float64(name):
     """the partial rows of one dgrad launch, summed, against float64 masked sums over the
     same bf16 gradient and BN input; dX bit-identical to the plain dgrad"""
-    planes, s, dil, n, variants = CASES[name]
+    planes, s, dil, n, modes = CASES[name]
     lib = L.load()
-    prev = {k: lib.mmad_set_kernel_variant(k.encode(), v) for k, v in variants.items()}
-    try:
+    with variants(**modes):
         g = torch.Generator(device=DEV).manual_seed(3)
         mk = lambda: torch.randn((n, planes, s, s, s), generator=g, device=DEV).to(  # noqa
             torch.bfloat16).contiguous(memory_format=CL)
@@ -122,9 +117,6 @@ def test_bnsum_partial_rows_vs_float64(name):
         dx2 = torch.empty_like(y)
         L.call("mmad_conv3d_dgrad", d, dt, L.ptr(gy), L.ptr(wpt), L.ptr(dx2), L.stream())
         torch.cuda.synchronize()
-    finally:
-        for k, v in prev.items():
-            lib.mmad_set_kernel_variant(k.encode(), v)
     assert torch.equal(dx, dx2)
     gd = dx.double().permute(0, 2, 3, 4, 1).reshape(-1, planes)
     yd = y.double().permute(0, 2, 3, 4, 1).reshape(-1, planes)

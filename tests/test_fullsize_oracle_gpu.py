@@ -47,6 +47,7 @@ import torch
 import multimodal_alzheimer_amd as M
 from oracle import prng
 from tests import _golden as G
+from tests._variants import variants
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -89,11 +90,8 @@ def _bench_routes():
     """The config-5 fixtures run at batch 2, where the 20^3 layer4 convs have too few
     residue-class blocks (128) for lattice5.hip's default rule; the bench runs them at batch
     8 through that kernel, so it is forced on here (it only matches 5d^3 grids)."""
-    from multimodal_alzheimer_amd import _lib
-    lib = _lib.load()
-    prev = lib.mmad_set_kernel_variant(b"lattice5", 2)
-    yield
-    lib.mmad_set_kernel_variant(b"lattice5", prev)
+    with variants(lattice5=2):
+        yield
 
 
 def _build(name, precision):

@@ -12,8 +12,8 @@ removed) is checked against a float64 weight gradient of the same bf16 operands,
 import pytest
 import torch
 
-from multimodal_alzheimer_amd import _lib
 from multimodal_alzheimer_amd import volume_ops as V
+from tests._variants import variants
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -43,16 +43,12 @@ def test_culled_conv_matches_fp32(name, xs, co, d):
         (3.0 / (xs[1] * 27)) ** 0.5
     xg = x.clone().requires_grad_(True)
     wg = w.clone().requires_grad_(True)
-    lib = _lib.load()
-    prev = lib.mmad_set_kernel_variant(b"lattice5", 0)
-    try:
+    with variants(lattice5=0):
         y = V.conv3d(xg, wg, None, (1,) * 3, (d,) * 3, (d,) * 3, BF)
         gy = (torch.rand(y.shape, generator=g, device=DEV) * 2 - 1).to(BF) \
             .contiguous(memory_format=CL)
         y.backward(gy)
         torch.cuda.synchronize()
-    finally:
-        lib.mmad_set_kernel_variant(b"lattice5", prev)
     xr = x.float().requires_grad_(True)
     yr = torch.nn.functional.conv3d(xr, w.to(BF).float(), None, 1, d, d)
     yr.backward(gy.float())

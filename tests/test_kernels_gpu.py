@@ -6,6 +6,7 @@ import torch
 import torch.nn.functional as F
 
 from multimodal_alzheimer_amd import _lib, head_ops, volume_ops as V
+from tests._variants import variants
 
 pytestmark = pytest.mark.gpu
 CL = torch.channels_last_3d
@@ -268,19 +269,15 @@ def test_bnpool_zwalk_kernel_matches_rows_kernel(shape):
     per-output rows kernel (0): pooled output, argmax-routed input gradient and BN parameter
     gradients bit-identical (ties on ReLU zeros everywhere)."""
     n, c = shape[:2]
-    lib = _lib.load()
     res = {}
     for mode in (0, 2):
         bn = _BN(c, 75)
         bn.training = True
         y = to_vol(rnd(*shape, seed=74, scale=2.0), torch.bfloat16).requires_grad_(True)
-        prev = lib.mmad_set_kernel_variant(b"pool_run", mode)
-        try:
+        with variants(pool_run=mode):
             p = V.batchnorm_relu_maxpool(y, bn, None, 3, 2, 1)
             p.backward(to_vol(rnd(*p.shape, seed=76), torch.bfloat16))
             torch.cuda.synchronize()
-        finally:
-            lib.mmad_set_kernel_variant(b"pool_run", prev)
         res[mode] = (p, y.grad, bn.weight.grad, bn.bias.grad)
     for nm, a, b in zip(("out", "dy", "dgamma", "dbeta"), res[0], res[2]):
         assert torch.equal(a, b), nm

@@ -10,17 +10,13 @@ x plane) and the profiler's kernel names."""
 import pytest
 import torch
 
-from multimodal_alzheimer_amd import _lib
 from multimodal_alzheimer_amd import volume_ops as V
+from tests._variants import variants
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 CL = torch.channels_last_3d
 BF = torch.bfloat16
-
-
-def _variant(v):
-    return _lib.load().mmad_set_kernel_variant(b"lattice5", v)
 
 
 def _kernels_of(fn):
@@ -57,16 +53,13 @@ def test_lattice5_matches_fp32(name, xs, co, d):
     x = (torch.rand(xs, generator=g, device=DEV) * 2 - 1).to(BF).contiguous(memory_format=CL)
     w = (torch.rand((co, xs[1], 3, 3, 3), generator=g, device=DEV) * 2 - 1) * \
         (3.0 / (xs[1] * 27)) ** 0.5
-    prev = _variant(2)
-    try:
+    with variants(lattice5=2):
         xg = x.clone().requires_grad_(True)
         wg = w.clone().requires_grad_(True)
         y, stats = V.conv3d(xg, wg, None, (1,) * 3, (d,) * 3, (d,) * 3, BF, want_stats=True)
         gy = (torch.rand(y.shape, generator=g, device=DEV) * 2 - 1).to(BF) \
             .contiguous(memory_format=CL)
         kernels = _kernels_of(lambda: y.backward(gy))
-    finally:
-        _variant(prev)
     if kernels is not None:
         assert any("lattice5_wgrad_kernel" in k for k in kernels), "weight gradient not routed"
         if xs[1] % 128 == 0:                 # (dX of 64 channels: 128-channel tiles only)
@@ -108,15 +101,11 @@ def test_lattice5_eval_epilogue_residual_relu():
         .contiguous(memory_format=CL)
     res = (torch.rand((8, 512, 20, 20, 20), generator=g, device=DEV) * 2 - 1).to(BF) \
         .contiguous(memory_format=CL)
-    prev = _variant(0)
-    try:
-        with torch.no_grad():
-            ref = V.conv_bn_act_eval(x, conv, bn, relu=True, res=res)
-            _variant(2)
+    with variants(lattice5=0), torch.no_grad():
+        ref = V.conv_bn_act_eval(x, conv, bn, relu=True, res=res)
+        with variants(lattice5=2):
             got = V.conv_bn_act_eval(x, conv, bn, relu=True, res=res)
         torch.cuda.synchronize()
-    finally:
-        _variant(prev)
     err = (got.float() - ref.float()).abs()
     assert (err <= 2 ** -6 * ref.float().abs() + 2e-2).all(), err.max().item()
     assert (got == 0).any() and (got > 0).any()

@@ -32,6 +32,7 @@ import torch.nn.functional as F
 
 from multimodal_alzheimer_amd import _lib as L
 from multimodal_alzheimer_amd import volume_ops as V
+from tests._variants import variants
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -105,17 +106,11 @@ def _launches(n, cs, nd, grid, seed, routed=True):
 
 def _on_off(n, cs, nd, grid, seed, routed):
     """the launches of one shape with the variant off (x-pair form), then on (x-walk)"""
-    lib = L.load()
-    prev = lib.mmad_set_kernel_variant(b"lattice8", 2)
-    prev_x = lib.mmad_set_kernel_variant(b"lattice8_xwalk", 0)
-    try:
-        assert prev_x in (0, 1), "unknown variant name"
+    with variants(lattice8=2, lattice8_xwalk=0) as prev:
+        assert prev["lattice8_xwalk"] in (0, 1), "unknown variant name"
         off = _launches(n, cs, nd, grid, seed, routed)
-        lib.mmad_set_kernel_variant(b"lattice8_xwalk", 1)
-        on = _launches(n, cs, nd, grid, seed, routed)
-    finally:
-        lib.mmad_set_kernel_variant(b"lattice8_xwalk", prev_x)
-        lib.mmad_set_kernel_variant(b"lattice8", prev)
+        with variants(lattice8_xwalk=1):
+            on = _launches(n, cs, nd, grid, seed, routed)
     return off, on
 
 

@@ -11,17 +11,13 @@ tests/test_fullsize_gpu.py."""
 import pytest
 import torch
 
-from multimodal_alzheimer_amd import _lib
 from multimodal_alzheimer_amd import volume_ops as V
+from tests._variants import variants
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 CL = torch.channels_last_3d
 BF = torch.bfloat16
-
-
-def _variant(v):
-    return _lib.load().mmad_set_kernel_variant(b"lattice_zp", v)
 
 
 def _conv(x, w, res=None):
@@ -41,13 +37,11 @@ def test_plane_pair_equals_one_plane(ci, co):
     x = (torch.rand((8, ci, 16, 16, 16), generator=g, device=DEV) * 2 - 1).to(BF) \
         .contiguous(memory_format=CL)
     w = (torch.rand((co, ci, 3, 3, 3), generator=g, device=DEV) * 2 - 1) * (3.0 / (ci * 27)) ** 0.5
-    prev = _variant(0)
-    try:
+    with variants(lattice_zp=0):
         ref = _conv(x, w)
-        assert _variant(1) == 0
-        got = _conv(x, w)
-    finally:
-        _variant(prev)
+        with variants(lattice_zp=1) as prev:
+            assert prev["lattice_zp"] == 0
+            got = _conv(x, w)
     assert torch.equal(got[0], ref[0]), "forward differs"
     assert torch.equal(got[2], ref[2]), "input gradient differs"
     assert torch.equal(got[3], ref[3]), "weight gradient differs"
@@ -74,13 +68,9 @@ def test_plane_pair_eval_epilogue_residual_relu():
         .contiguous(memory_format=CL)
     res = (torch.rand((8, 512, 16, 16, 16), generator=g, device=DEV) * 2 - 1).to(BF) \
         .contiguous(memory_format=CL)
-    prev = _variant(0)
-    try:
-        with torch.no_grad():
-            ref = V.conv_bn_act_eval(x, conv, bn, relu=True, res=res)
-            _variant(1)
+    with variants(lattice_zp=0), torch.no_grad():
+        ref = V.conv_bn_act_eval(x, conv, bn, relu=True, res=res)
+        with variants(lattice_zp=1):
             got = V.conv_bn_act_eval(x, conv, bn, relu=True, res=res)
         torch.cuda.synchronize()
-    finally:
-        _variant(prev)
     assert torch.equal(got, ref)

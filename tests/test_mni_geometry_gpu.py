@@ -20,6 +20,7 @@ import multimodal_alzheimer_amd as M
 from multimodal_alzheimer_amd import _lib
 from multimodal_alzheimer_amd import volume_ops as V
 from tests import _golden as G
+from tests._variants import variants
 from tests.test_fullsize_gpu import _check, _ref_conv
 
 pytestmark = pytest.mark.gpu
@@ -75,8 +76,7 @@ def test_mni_model_bf16_tracks_reference():
     batch = {k: v.to(DEV) for k, v in G.batch_of("anat_r10_mni", g).items()}
     m.train()
     lib = _lib.load()
-    prev = (lib.mmad_set_kernel_variant(b"lattice", 2), lib.mmad_set_kernel_variant(b"lattice8", 2))
-    try:
+    with variants(lattice=2, lattice8=2):
         d4 = V.conv_desc((2, 512) + GRID, (512, 512, 3, 3, 3), (1,) * 3, (4,) * 3, (4,) * 3)
         d2 = V.conv_desc((2, 256) + GRID, (256, 256, 3, 3, 3), (1,) * 3, (2,) * 3, (2,) * 3)
         assert lib.mmad_conv3d_stats_rows(d4, _lib.BF16) == 2 * 2 * 3     # residue-class
@@ -84,9 +84,6 @@ def test_mni_model_bf16_tracks_reference():
         out = m.general_step(batch, 0, "train")
         out["loss"].backward()
         torch.cuda.synchronize()
-    finally:
-        lib.mmad_set_kernel_variant(b"lattice", prev[0])
-        lib.mmad_set_kernel_variant(b"lattice8", prev[1])
     got = out["outputs"].detach().cpu().numpy()
     ref = g["train_logits"]
     bound = 3e-2 * max(1.0, np.abs(ref).max())

@@ -10,17 +10,13 @@ round-4 weight-stationary form measured no faster and was removed in round 5.)""
 import pytest
 import torch
 
-from multimodal_alzheimer_amd import _lib
 from multimodal_alzheimer_amd import volume_ops as V
+from tests._variants import variants
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 CL = torch.channels_last_3d
 BF = torch.bfloat16
-
-
-def _variant(name, v):
-    return _lib.load().mmad_set_kernel_variant(name.encode(), v)
 
 
 def _conv(x, w):
@@ -61,13 +57,10 @@ def test_patchz_matches_patch_and_fp32(n, size, mode):
     x = (torch.rand((n, 64, size, size, size), generator=g, device=DEV) * 2 - 1).to(BF) \
         .contiguous(memory_format=CL)
     w = (torch.rand((64, 64, 3, 3, 3), generator=g, device=DEV) * 2 - 1) * (3.0 / (64 * 27)) ** 0.5
-    prev = _variant("patchz", 0)
-    try:
+    with variants(patchz=0):
         ref = _conv(x, w)
-        _variant("patchz", mode)
-        got = _conv(x, w)
-    finally:
-        _variant("patchz", prev)
+        with variants(patchz=mode):
+            got = _conv(x, w)
     assert got[4] == n * (size // 4) * (size // 8) ** 2, "not routed to the z-walking kernel"
     assert torch.equal(got[3], ref[3]), "weight gradient differs (same wgrad kernel)"
     assert torch.equal(got[0], ref[0]), "forward differs"
@@ -94,13 +87,9 @@ def test_patchz_eval_epilogue_residual_relu():
         .contiguous(memory_format=CL)
     res = (torch.rand((8, 64, 32, 32, 32), generator=g, device=DEV) * 2 - 1).to(BF) \
         .contiguous(memory_format=CL)
-    prev = _variant("patchz", 0)
-    try:
-        with torch.no_grad():
-            ref = V.conv_bn_act_eval(x, conv, bn, relu=True, res=res)
-            _variant("patchz", 1)
+    with variants(patchz=0), torch.no_grad():
+        ref = V.conv_bn_act_eval(x, conv, bn, relu=True, res=res)
+        with variants(patchz=1):
             got = V.conv_bn_act_eval(x, conv, bn, relu=True, res=res)
         torch.cuda.synchronize()
-    finally:
-        _variant("patchz", prev)
     assert torch.equal(got, ref)

@@ -18,8 +18,8 @@ is a race, not a fault, and shows up there.  Plus the eval epilogue (residual + 
 import pytest
 import torch
 
-from multimodal_alzheimer_amd import _lib
 from multimodal_alzheimer_amd import volume_ops as V
+from tests._variants import variants
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -29,10 +29,6 @@ BF = torch.bfloat16
 # (N, D, H, W, output channels)
 CASES = [(1, 8, 8, 8, 64), (1, 12, 8, 8, 64), (2, 28, 16, 8, 64), (1, 12, 8, 8, 128)]
 IDS = ["two_boxes", "three_boxes", "seven_boxes_two_columns", "two_channel_tiles"]
-
-
-def _variant(name, v):
-    return _lib.load().mmad_set_kernel_variant(name.encode(), v)
 
 
 def _conv(x, w, gy=None):
@@ -58,14 +54,11 @@ def runs(request):
     x = (torch.rand((n, 64, d, h, wd), generator=g, device=DEV) * 2 - 1).to(BF) \
         .contiguous(memory_format=CL)
     w = (torch.rand((co, 64, 3, 3, 3), generator=g, device=DEV) * 2 - 1) * (3.0 / (64 * 27)) ** 0.5
-    prev = _variant("patchz", 0)
-    try:
+    with variants(patchz=0):
         ref = _conv(x, w)
-        _variant("patchz", 2)
-        got = _conv(x, w, ref["gy"])
-        again = _conv(x, w, ref["gy"])
-    finally:
-        _variant("patchz", prev)
+        with variants(patchz=2):
+            got = _conv(x, w, ref["gy"])
+            again = _conv(x, w, ref["gy"])
     xr = x.float().requires_grad_(True)
     wr = w.to(BF).float().requires_grad_(True)
     yr = _ref_conv(xr, wr, 1, 1, 1)
@@ -129,16 +122,12 @@ def test_eval_epilogue_residual_relu():
     shape = (1, 64, 12, 8, 8)
     x = (torch.rand(shape, generator=g, device=DEV) * 2 - 1).to(BF).contiguous(memory_format=CL)
     res = (torch.rand(shape, generator=g, device=DEV) * 2 - 1).to(BF).contiguous(memory_format=CL)
-    prev = _variant("patchz", 0)
-    try:
-        with torch.no_grad():
-            ref = V.conv_bn_act_eval(x, conv, bn, relu=True, res=res)
-            _variant("patchz", 2)
+    with variants(patchz=0), torch.no_grad():
+        ref = V.conv_bn_act_eval(x, conv, bn, relu=True, res=res)
+        with variants(patchz=2):
             got = V.conv_bn_act_eval(x, conv, bn, relu=True, res=res)
             again = V.conv_bn_act_eval(x, conv, bn, relu=True, res=res)
         torch.cuda.synchronize()
-    finally:
-        _variant("patchz", prev)
     assert (ref > 0).any() and (ref == 0).any(), "the ReLU clips nothing or everything"
     assert torch.equal(got, ref)
     assert torch.equal(again, got)

@@ -15,8 +15,6 @@ buffer between two 512-byte margins; the test-made operands sit between NaN marg
 The shapes are the small ones of the op's own tests (partial tiles, several splits), the
 specialised conv routes are forced at batch 1 and checked through the BN partial-sum row
 count and the profiler's kernel names."""
-import contextlib
-
 import numpy as np
 import pytest
 import torch
@@ -29,6 +27,7 @@ from multimodal_alzheimer_amd import layers as Lyr
 from multimodal_alzheimer_amd import volume_ops as V
 from tests import _golden as G
 from tests import _poison as P
+from tests._variants import variants
 from tests.test_kernels_gpu import CONV_CASES, _BN, _ref_bn, close, rnd, to_vol
 
 pytestmark = pytest.mark.gpu
@@ -75,21 +74,6 @@ def run3(fn, bar=None, kernels=()):
     if bar is not None:
         bar(out["plain"])                                                        # (d)
     return out["plain"]
-
-
-@contextlib.contextmanager
-def variants(**modes):
-    """mmad_set_kernel_variant(name, mode) for the block; the previous modes afterwards"""
-    lib = L.load()
-    prev = {}
-    try:
-        for k, v in modes.items():
-            prev[k] = lib.mmad_set_kernel_variant(k.encode(), v)
-            assert prev[k] >= 0, f"unknown kernel variant {k}"
-        yield
-    finally:
-        for k, v in prev.items():
-            lib.mmad_set_kernel_variant(k.encode(), v)
 
 
 def _dev_vol(shape, gen, dtype=BF, normal=False):

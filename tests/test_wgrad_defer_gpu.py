@@ -8,6 +8,7 @@ import torch
 
 from multimodal_alzheimer_amd import _lib
 from multimodal_alzheimer_amd import volume_ops as V
+from tests._variants import variants
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -154,15 +155,11 @@ def test_stride2_3cube_wgrad_dedup_bit_identical(xs, co):
     (pw_wgrad_kernel MODE 4: the even input columns and the 17 odd ones of each output row
     staged once, read by kx = 1 and by kx = 0 / 2 at a one-row offset) gives exactly the
     three-image form's dW (MODE 2): the same voxel pairs summed in the same order."""
-    lib = _lib.load()
     x, w = _operands(xs, (co, xs[1], 3, 3, 3), 13)
-    prev = lib.mmad_set_kernel_variant(b"pw_wg3_dedup", 0)
-    try:
+    with variants(pw_wg3_dedup=0):
         ref, gy, _ = _wgrad(x, w, 2, 1, 1)
-        lib.mmad_set_kernel_variant(b"pw_wg3_dedup", 1)
-        got, _, _ = _wgrad(x, w, 2, 1, 1, gy)
-    finally:
-        lib.mmad_set_kernel_variant(b"pw_wg3_dedup", prev)
+        with variants(pw_wg3_dedup=1):
+            got, _, _ = _wgrad(x, w, 2, 1, 1, gy)
     assert torch.equal(got, ref), f"max |diff| {(got - ref).abs().max().item():.3e}"
 
 
