@@ -147,6 +147,52 @@ typedef struct mmad_adam_job {
 int64_t mmad_adam_job_tiles(const mmad_adam_job* job);
 int mmad_adam_repack(int njobs, const mmad_adam_job* jobs_device, const int* block_job,
                      int64_t total_tiles, int* arrivals, void* stream);
+/* ---- Gradient guard: global-norm clipping and non-finite-step skipping ------------
+ * One pass over a step's gradients (contiguous fp32) gives their global L2 norm, the clip
+ * coefficient and a non-finite flag on the device; nothing is read back by the host.  One job
+ * per gradient, cut into flat chunks of 4096 elements: chunk0 = the job's first chunk of the
+ * launch (jobs sorted by chunk0, total_chunks = their sum).  `state` is float64[10]:
+ *   [0] max_norm (caller; +inf = do not clip)   [1] skip_nonfinite (caller; 0 / 1)
+ *   [2] sumsq   [3] norm = sqrt(sumsq)   [4] coef (the float32 coefficient, widened)
+ *   [5] skip (1: this step is to be skipped)   [6] steps   [7] clipped (coef < 1)
+ *   [8] skipped   [9] reserved, 0            -- [2..9] written by mmad_grad_guard_finalize.
+ * njobs <= 0 is a no-op (MMAD_OK); a null pointer is MMAD_ENULL; nblocks <= 0 (or above 1024)
+ * with work to do is MMAD_EBADSHAPE. */
+typedef struct mmad_grad_job {
+  const float* grad;
+  int64_t numel;
+  int64_t chunk0;
+} mmad_grad_job;
+/* blocks of a mmad_grad_sumsq launch = slots of `partials`: min(total_chunks, 1024) */
+int mmad_grad_guard_blocks(int64_t total_chunks);
+/* Replaces the norm half of torch.nn.utils.clip_grad_norm_ (torch/nn/utils/clip_grad.py:
+ * _foreach_norm per tensor, stack, norm; Lightning's Trainer(gradient_clip_val=...) and
+ * track_grad_norm call it) with one launch: block b sums the squares of chunks b, b + nblocks,
+ * ... in double and writes partials[b]; every slot is written on every launch, no atomics, and
+ * the value is bitwise reproducible across launches. */
+int mmad_grad_sumsq(int njobs, const mmad_grad_job* jobs_device, int64_t total_chunks,
+                    int nblocks, double* partials, void* stream);
+/* Replaces clip_grad_norm_'s coefficient (clip_grad.py:165-169: clamp(max_norm / (total_norm +
+ * 1e-6), max=1.0), evaluated in float32 from the float32-rounded norm) and the found_inf
+ * reduction of torch's grad scaler (torch.amp.GradScaler._unscale_grads_): one block folds
+ * partials[0 .. nblocks) in index order and writes state[2..9]; nonfinite = !isfinite(sumsq),
+ * skip = nonfinite && state[1].  A second launch on purpose (the kernel boundary orders the
+ * partials; no in-launch hand-off). */
+int mmad_grad_guard_finalize(int nblocks, const double* partials, double* state, void* stream);
+/* Replaces clip_grad_norm_'s _foreach_mul_(grads, coef) (Lightning's gradient_clip_val applies
+ * it): g *= (float)state[4] in place, nothing when state[5] is set. */
+int mmad_grad_scale(int njobs, const mmad_grad_job* jobs_device, int64_t total_chunks,
+                    const double* state, void* stream);
+/* mmad_adam_repack under a guard; replaces clip_grad_norm_'s multiply followed by torch fused
+ * Adam's found_inf path (torch.optim.Adam(fused=True) with found_inf set: no update, no step
+ * increment).  state[5] != 0: every block returns before its first store -- parameters, both
+ * moments, step counters, packed layouts and arrivals stay bit for bit.  Otherwise the update
+ * reads grad * (float)state[4], rounded to float32 before the weight-decay term is added
+ * (g.mul_(coef) then torch's Adam); a coefficient of 1 gives mmad_adam_repack's bits.  The
+ * gradients themselves are not rewritten. */
+int mmad_adam_repack_guarded(int njobs, const mmad_adam_job* jobs_device, const int* block_job,
+                             int64_t total_tiles, int* arrivals, const double* state,
+                             void* stream);
 int64_t mmad_conv_unfolded_elems(const mmad_conv_desc* d);
 int mmad_conv_unfold_input(const mmad_conv_desc* d, int in_dtype, const void* x,
                            int dtype, void* x_unf, void* stream);

@@ -55,6 +55,11 @@ class AdamJob(C.Structure):
                 [(n, C.c_int64) for n in ("numel", "tile0", "ntiles")])
 
 
+class GradJob(C.Structure):
+    """mirror of mmad_grad_job (include/mmad.h)"""
+    _fields_ = [("grad", C.c_void_p), ("numel", C.c_int64), ("chunk0", C.c_int64)]
+
+
 class BnFin(C.Structure):
     """mirror of mmad_bn_fin (include/mmad.h)"""
     _fields_ = ([("nparts", C.c_int32)] +
@@ -104,6 +109,11 @@ _SIGS = {
     "mmad_conv_pack_dual_batch": (_i32, [_i32, _i32, _vp, _i64, _vp]),
     "mmad_adam_job_tiles": (_i64, [_PA]),
     "mmad_adam_repack": (_i32, [_i32, _vp, _vp, _i64, _vp, _vp]),
+    "mmad_grad_guard_blocks": (_i32, [_i64]),
+    "mmad_grad_sumsq": (_i32, [_i32, _vp, _i64, _i32, _vp, _vp]),
+    "mmad_grad_guard_finalize": (_i32, [_i32, _vp, _vp, _vp]),
+    "mmad_grad_scale": (_i32, [_i32, _vp, _i64, _vp, _vp]),
+    "mmad_adam_repack_guarded": (_i32, [_i32, _vp, _vp, _i64, _vp, _vp, _vp]),
     "mmad_conv_unfolded_elems": (_i64, [_P]),
     "mmad_conv_unfold_input": (_i32, [_P, _i32, _vp, _i32, _vp, _vp]),
     "mmad_conv3d_stats_rows": (_i64, [_P, _i32]),

@@ -47,11 +47,37 @@ __device__ __forceinline__ bool al16(const void* p) {
   return (reinterpret_cast<uintptr_t>(p) & 15) == 0;
 }
 
+// the gradient the update sees: under a guard (fused_optim.GradGuard, gradguard.hip) the
+// clipped one, rounded to float32 before anything else reads it -- what g.mul_(coef) in front
+// of torch's Adam leaves; g * 1.0f is g
+template <bool GUARD>
+__device__ __forceinline__ float guarded(float g, float coef) {
+  if constexpr (GUARD) return __fmul_rn(g, coef);
+  else return g;
+}
+
+__device__ __forceinline__ const double* guard_state(const double* state) { return state; }
+
+// One kernel, two instantiations: State empty = the plain step (mmad_adam_repack: this
+// signature and this code, nothing of the guard in it); State = one `const double*` = the
+// guarded step (mmad_adam_repack_guarded), whose argument is the guard's float64[10] (slot 4
+// the clip coefficient, slot 5 the skip flag).  A skipped step returns before the block's first
+// store -- parameters, moments, step counters, packed layouts and arrival counters stay as they
+// were (torch's fused Adam under found_inf: no update, no step increment).
+template <typename... State>
 __global__ __launch_bounds__(NT) void adam_repack_kernel(const mmad_adam_job* __restrict__ jobs,
                                                          int njobs,
                                                          const int* __restrict__ block_job,
-                                                         int* __restrict__ arrivals) {
+                                                         int* __restrict__ arrivals,
+                                                         State... state) {
+  constexpr bool GUARD = sizeof...(State) != 0;
   __shared__ float tile[16 * 27 * 17];
+  float coef = 1.0f;
+  if constexpr (GUARD) {
+    const double* st = guard_state(state...);
+    if (st[5] != 0.0) return;           // (block-uniform)
+    coef = (float)st[4];
+  }
   int lo = 0, hi = njobs - 1;
   const int64_t bid = blockIdx.x;
   if (block_job != nullptr) {
@@ -100,7 +126,7 @@ __global__ __launch_bounds__(NT) void adam_repack_kernel(const mmad_adam_job* __
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           float mq = m[q], vq = v[q];
-          o[q] = adam_elem(k, p[q], g[q], mq, vq);
+          o[q] = adam_elem(k, p[q], guarded<GUARD>(g[q], coef), mq, vq);
           m[q] = mq;
           v[q] = vq;
         }
@@ -111,7 +137,7 @@ __global__ __launch_bounds__(NT) void adam_repack_kernel(const mmad_adam_job* __
     } else {
       for (int64_t e = e0 + threadIdx.x; e < e1; e += NT) {
         float m = M[e], v = Q[e];
-        P[e] = adam_elem(k, P[e], G[e], m, v);
+        P[e] = adam_elem(k, P[e], guarded<GUARD>(G[e], coef), m, v);
         M[e] = m;
         Q[e] = v;
       }
@@ -152,7 +178,7 @@ __global__ __launch_bounds__(NT) void adam_repack_kernel(const mmad_adam_job* __
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           float mq = m[q], vq = v[q];
-          w[q] = adam_elem(k, p[q], g[q], mq, vq);
+          w[q] = adam_elem(k, p[q], guarded<GUARD>(g[q], coef), mq, vq);
           m[q] = mq;
           v[q] = vq;
           const int rem = rem0 + q, cil = rem / T, tap = rem % T;
@@ -167,7 +193,7 @@ __global__ __launch_bounds__(NT) void adam_repack_kernel(const mmad_adam_job* __
         const int col = e / per_co, rem = e % per_co;
         const int64_t o = ((int64_t)(co0 + col) * CI + ci0) * T + rem;
         float m = M[o], v = Q[o];
-        const float w = adam_elem(k, P[o], G[o], m, v);
+        const float w = adam_elem(k, P[o], guarded<GUARD>(G[o], coef), m, v);
         P[o] = w;
         M[o] = m;
         Q[o] = v;
@@ -230,8 +256,20 @@ int mmad_adam_repack(int njobs, const mmad_adam_job* jobs_device, const int* blo
   if (njobs <= 0 || total_tiles <= 0) return MMAD_OK;
   if (jobs_device == nullptr || arrivals == nullptr || total_tiles > 0x7fffffff)
     return MMAD_ENULL;
-  hipLaunchKernelGGL(adam_repack_kernel, dim3((unsigned)total_tiles), dim3(NT), 0,
+  hipLaunchKernelGGL(adam_repack_kernel<>, dim3((unsigned)total_tiles), dim3(NT), 0,
                      as_stream(stream), jobs_device, njobs, block_job, arrivals);
+  return launch_status();
+}
+
+int mmad_adam_repack_guarded(int njobs, const mmad_adam_job* jobs_device, const int* block_job,
+                             int64_t total_tiles, int* arrivals, const double* state,
+                             void* stream) {
+  if (njobs <= 0 || total_tiles <= 0) return MMAD_OK;
+  if (jobs_device == nullptr || arrivals == nullptr || state == nullptr ||
+      total_tiles > 0x7fffffff)
+    return MMAD_ENULL;
+  hipLaunchKernelGGL(adam_repack_kernel<const double*>, dim3((unsigned)total_tiles), dim3(NT),
+                     0, as_stream(stream), jobs_device, njobs, block_job, arrivals, state);
   return launch_status();
 }
 

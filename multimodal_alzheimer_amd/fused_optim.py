@@ -20,9 +20,30 @@ parameter was modified outside the graph, seen through its ``_version``).
 Supported: ``torch.optim.Adam`` (and subclasses that keep its ``step``) with fused=True,
 amsgrad / maximize / differentiable / decoupled weight decay off, float betas, fp32
 parameters and state, no gradient scaler.  ``supported(optimizer)`` says whether it
-applies; the caller keeps ``optimizer.step()`` otherwise."""
+applies; the caller keeps ``optimizer.step()`` otherwise.
+
+Gradient guard.  ``GradGuard`` measures the global L2 norm of the gradients in one bandwidth
+pass (csrc/gradguard.hip: ``mmad_grad_sumsq`` + ``mmad_grad_guard_finalize``) and leaves, in a
+float64[10] device tensor ``state`` (slot names below), the norm, the clip coefficient of
+``torch.nn.utils.clip_grad_norm_`` and a skip flag for a step whose gradients hold an Inf or a
+NaN.  Two consumers:
+
+* ``AdamRepack(optimizer, plans, guard=guard)``: ``step()`` measures, then launches
+  ``mmad_adam_repack_guarded``, which multiplies each gradient by the coefficient on its way
+  into the update (bit for bit ``g.mul_(coef)`` followed by torch's Adam) and does nothing at
+  all on a skipped step (torch's fused Adam under ``found_inf``).  ``p.grad`` is NOT rewritten:
+  after a guarded step it still holds the unclipped gradient, and ``state`` says what was
+  applied.
+* ``clip_grad_norm_(parameters, max_norm, guard=None)``: the eager form for hand-written loops,
+  ``guard.measure()`` then ``guard.apply_()`` (``mmad_grad_scale`` rewrites the gradients in
+  place), a drop-in for the torch function that returns the norm without a host sync.
+
+The threshold and the skip switch live in ``state`` and are read by the kernels, so
+``set_max_norm`` / ``set_skip_nonfinite`` between two replays of a captured step take effect
+without a re-capture."""
 import ctypes as C
 import inspect
+import math
 import os
 
 import torch
@@ -31,6 +52,18 @@ from . import _lib as L
 
 # MMAD_ADAM_REPACK=0: captured steps keep torch's fused Adam and the in-forward repack (A/B)
 ENABLED = os.environ.get("MMAD_ADAM_REPACK", "1") != "0"
+# MMAD_GRAD_GUARD=<float>: graph_step.GraphedTrainStep built without clip_grad_norm= /
+# skip_nonfinite= gets a GradGuard with this max_norm (inf: measure and skip only) and
+# skip_nonfinite=True; unset: no guard
+GRAD_GUARD = os.environ.get("MMAD_GRAD_GUARD") or None
+
+# slots of GradGuard.state (float64[10]; include/mmad.h)
+MAX_NORM, SKIP_NONFINITE, SUMSQ, NORM, COEF, SKIP, STEPS, CLIPPED, SKIPPED, RESERVED = range(10)
+STATE_SLOTS = 10
+STATE_NAMES = ("max_norm", "skip_nonfinite", "sumsq", "norm", "coef", "skip", "steps",
+               "clipped", "skipped", "reserved")
+GRAD_CHUNK = 4096                 # elements per chunk of a gradient job (csrc/gradguard.hip)
+GRAD_MAX_BLOCKS = 1024            # slots of GradGuard.partials
 
 
 def supported(optimizer):
@@ -71,11 +104,192 @@ def pack_plans(model):
     return out
 
 
+def check_max_norm(max_norm):
+    """``max_norm`` as a float: None = +inf (measure only); non-positive or NaN raises"""
+    if max_norm is None:
+        return math.inf
+    if isinstance(max_norm, bool) or torch.is_tensor(max_norm):
+        raise ValueError(f"max_norm must be a positive number or None, not {max_norm!r}")
+    try:
+        v = float(max_norm)
+    except (TypeError, ValueError):
+        raise ValueError(f"max_norm must be a positive number or None, not {max_norm!r}") from None
+    if math.isnan(v) or v <= 0.0:
+        raise ValueError(f"max_norm must be positive (None or inf: do not clip), got {max_norm!r}")
+    return v
+
+
+def guard_settings(clip_grad_norm=None, skip_nonfinite=False, env=None):
+    """What GraphedTrainStep's guard arguments ask for: ``None`` (no guard) or ``(max_norm,
+    skip_nonfinite)``.  ``env`` (the value of MMAD_GRAD_GUARD) counts only when both arguments
+    are at their defaults: that max_norm and skip_nonfinite=True."""
+    if clip_grad_norm is None and not skip_nonfinite:
+        if env is None or env == "":
+            return None
+        try:
+            v = float(env)
+        except ValueError:
+            raise ValueError(f"MMAD_GRAD_GUARD must be a positive number or inf, got {env!r}") \
+                from None
+        return check_max_norm(v), True
+    return check_max_norm(clip_grad_norm), bool(skip_nonfinite)
+
+
+class GradGuard:
+    """Global gradient norm, clip coefficient and non-finite flag of a set of parameters, on
+    the device (module docstring).  ``params_or_optimizer``: an optimizer (its groups'
+    parameters), an iterable of tensors or one tensor; parameters without a gradient when
+    ``measure()`` runs are left out, as torch leaves them out.  ``max_norm=None`` is +inf: the
+    norm is measured and nothing is clipped."""
+
+    def __init__(self, params_or_optimizer, max_norm=None, skip_nonfinite=True):
+        self._max_norm = check_max_norm(max_norm)
+        self._skip_nonfinite = bool(skip_nonfinite)
+        if isinstance(params_or_optimizer, torch.optim.Optimizer):
+            ps = [p for g in params_or_optimizer.param_groups for p in g["params"]]
+        elif torch.is_tensor(params_or_optimizer):
+            ps = [params_or_optimizer]
+        else:
+            ps = list(params_or_optimizer)
+        if any(not torch.is_tensor(p) for p in ps):
+            raise ValueError("GradGuard: parameters must be tensors")
+        self.params = ps
+        self.state = self.partials = self.table = None
+        self.njobs = self.chunks = self.nblocks = 0
+        self._host = self._committed = b""
+
+    def prepare(self, device):
+        """allocate the state, the block partials and the device job table (before a capture:
+        nothing may be allocated from the host inside one)"""
+        self.state = torch.zeros(STATE_SLOTS, dtype=torch.float64, device=device)
+        self.state[MAX_NORM].fill_(self._max_norm)
+        self.state[SKIP_NONFINITE].fill_(float(self._skip_nonfinite))
+        self.partials = torch.empty(GRAD_MAX_BLOCKS, dtype=torch.float64, device=device)
+        self.table = torch.empty(max(len(self.params), 1) * C.sizeof(L.GradJob),
+                                 dtype=torch.uint8, device=device)
+        self._committed = b""
+
+    def _device(self):
+        for p in self.params:
+            if p.is_cuda:
+                return p.device
+        raise L.MMADError("GradGuard runs on HIP devices only: no parameter is on one")
+
+    def _jobs(self):
+        jobs, chunks = [], 0
+        for p in self.params:
+            g = p.grad
+            if g is None or g.numel() == 0:
+                continue
+            if not g.is_cuda or g.dtype != torch.float32 or not g.is_contiguous():
+                raise ValueError("GradGuard: gradients must be contiguous fp32 device tensors")
+            j = L.GradJob()
+            j.grad, j.numel, j.chunk0 = g.data_ptr(), g.numel(), chunks
+            chunks += (g.numel() + GRAD_CHUNK - 1) // GRAD_CHUNK
+            jobs.append(j)
+        return jobs, chunks
+
+    def measure(self):
+        """launch the norm pass and its finalize on the current stream (capturable: the job
+        table of the gradients present now is written by ``commit()``, outside capture)"""
+        if self.state is None:
+            self.prepare(self._device())
+        jobs, chunks = self._jobs()
+        if len(jobs) * C.sizeof(L.GradJob) > self.table.numel():
+            raise ValueError("GradGuard: more jobs than prepared")
+        self.njobs, self.chunks = len(jobs), chunks
+        self.nblocks = L.load().mmad_grad_guard_blocks(chunks)
+        self._host = bytes((L.GradJob * len(jobs))(*jobs)) if jobs else b""
+        if not torch.cuda.is_current_stream_capturing():
+            self.commit()
+        L.call("mmad_grad_sumsq", self.njobs, L.ptr(self.table), self.chunks, self.nblocks,
+               L.ptr(self.partials), L.stream())
+        L.call("mmad_grad_guard_finalize", self.nblocks, L.ptr(self.partials),
+               L.ptr(self.state), L.stream())
+
+    def commit(self):
+        """copy the job table built by the last ``measure()`` to the device (outside capture;
+        nothing to do while the gradients stay where they were)"""
+        if self._host and self._host != self._committed:
+            host = torch.frombuffer(bytearray(self._host), dtype=torch.uint8)
+            self.table[:host.numel()].copy_(host)
+            self._committed = self._host
+
+    def apply_(self):
+        """``g *= coef`` in place over the gradients of the last ``measure()`` (nothing on a
+        step to be skipped)"""
+        if self.state is None:
+            raise ValueError("GradGuard.apply_: call measure() first")
+        L.call("mmad_grad_scale", self.njobs, L.ptr(self.table), self.chunks,
+               L.ptr(self.state), L.stream())
+
+    def set_max_norm(self, max_norm):
+        """new clip threshold (None / inf: do not clip), in place: the next launch or replay
+        reads it"""
+        self._max_norm = check_max_norm(max_norm)
+        if self.state is not None:
+            self.state[MAX_NORM].fill_(self._max_norm)
+
+    def set_skip_nonfinite(self, on):
+        self._skip_nonfinite = bool(on)
+        if self.state is not None:
+            self.state[SKIP_NONFINITE].fill_(float(self._skip_nonfinite))
+
+    @property
+    def max_norm(self):
+        return self._max_norm
+
+    @property
+    def skip_nonfinite(self):
+        return self._skip_nonfinite
+
+    # 0-d device views of the state: reading one into Python is the caller's sync
+    @property
+    def norm(self):
+        return self.state[NORM]
+
+    @property
+    def coef(self):
+        return self.state[COEF]
+
+    @property
+    def skip(self):
+        return self.state[SKIP]
+
+    def stats(self):
+        """the state as a dict of Python numbers (one host sync)"""
+        vals = self.state.tolist()
+        out = dict(zip(STATE_NAMES, vals))
+        for k in ("skip_nonfinite", "skip", "steps", "clipped", "skipped"):
+            out[k] = int(out[k])
+        del out["reserved"]
+        return out
+
+
+def clip_grad_norm_(parameters, max_norm, guard=None):
+    """``torch.nn.utils.clip_grad_norm_(parameters, max_norm)`` (L2) in three launches and no
+    host sync: measure, finalize, scale in place.  Returns the total norm as a 0-d float64
+    device tensor, a view of ``guard.state`` that the next call overwrites.  ``guard``: a
+    GradGuard over the same parameters, kept between calls (its buffers and job table are
+    reused, its ``max_norm`` follows this call's); without one a fresh guard is built, which
+    never skips (a non-finite norm propagates into the gradients, as in torch)."""
+    if guard is None:
+        guard = GradGuard(parameters, max_norm, skip_nonfinite=False)
+    elif check_max_norm(max_norm) != guard.max_norm:
+        guard.set_max_norm(max_norm)
+    guard.measure()
+    guard.apply_()
+    return guard.norm
+
+
 class AdamRepack:
-    def __init__(self, optimizer, plans=()):
+    def __init__(self, optimizer, plans=(), guard=None):
+        """``guard``: a GradGuard over the optimizer's parameters; ``step()`` then measures
+        the gradients and launches the guarded update (module docstring)"""
         if not supported(optimizer):
             raise ValueError("AdamRepack: optimizer configuration not supported")
         self.optimizer = optimizer
+        self.guard = guard
         self.plans = [p for p in plans if p.nduals or p.unfolds]
         self.table = None
         self.njobs = self.tiles = 0
@@ -152,6 +366,8 @@ class AdamRepack:
                 if p.dim() == 5:
                     blocks += p.shape[0] // 16 * max(p.shape[1] // 16, 1) + p.shape[0]
         self.block_job = torch.zeros(max(blocks, 1), dtype=torch.int32, device=device)
+        if self.guard is not None and self.guard.state is None:
+            self.guard.prepare(device)
 
     def step(self):
         """launch the fused update on the current stream (capturable: the job table is
@@ -170,11 +386,20 @@ class AdamRepack:
             torch.tensor([j.ntiles for j in jobs], dtype=torch.int64)) if jobs else None
         if not torch.cuda.is_current_stream_capturing():
             self.commit()
-        L.call("mmad_adam_repack", self.njobs, L.ptr(self.table), L.ptr(self.block_job),
-               self.tiles, L.ptr(self.arrivals), L.stream())
+        if self.guard is None:
+            L.call("mmad_adam_repack", self.njobs, L.ptr(self.table), L.ptr(self.block_job),
+                   self.tiles, L.ptr(self.arrivals), L.stream())
+        else:
+            self.guard.measure()
+            L.call("mmad_adam_repack_guarded", self.njobs, L.ptr(self.table),
+                   L.ptr(self.block_job), self.tiles, L.ptr(self.arrivals),
+                   L.ptr(self.guard.state), L.stream())
 
     def commit(self):
-        """copy the job table built by the last ``step()`` to the device (outside capture)"""
+        """copy the job table built by the last ``step()`` to the device (outside capture),
+        and the guard's"""
+        if self.guard is not None:
+            self.guard.commit()
         if self._host:
             host = torch.frombuffer(bytearray(self._host), dtype=torch.uint8)
             self.table[:host.numel()].copy_(host)

@@ -47,6 +47,29 @@ depends on it:
 * dropout draws its seed on the device (``head_ops.dropout``), so every replay gets a
   fresh mask.
 
+``clip_grad_norm=`` / ``skip_nonfinite=`` put a gradient guard (``fused_optim.GradGuard``,
+``self.guard``) between the backward and Adam, where no host code can go: two small launches
+measure the global L2 norm of the final gradients, and the captured Adam
+(``mmad_adam_repack_guarded``) scales each gradient by the ``clip_grad_norm_`` coefficient as it
+reads it and does nothing at all on a step whose gradients hold an Inf or a NaN
+(``skip_nonfinite``).  The launches sit immediately in front of the captured Adam, after the
+gradients are final: in ``opt_graph`` for ``"after"`` / ``"staged"`` (captured after
+``reducer.finish()``), after ``reducer.finish()`` for ``"inside"``, after
+``flush_wgrad_reduce()`` with no reducer.  Data-parallel ranks take no extra collective: the
+all-reduced buckets are assumed bitwise identical on every rank (one all-reduce result, copied
+back in place), so every rank computes the same norm, coefficient and skip decision.  The
+threshold lives on the device: ``gs.guard.set_max_norm(v)`` / ``set_skip_nonfinite(b)`` take
+effect on the next replay, ``gs.guard.norm`` is the last step's norm without a sync and
+``gs.guard.stats()`` the counters with one.  ``p.grad`` is not rewritten by a replay: it holds
+the unclipped gradient.  The eager warm-up steps run the eager form (measure, scale in place,
+``optimizer.step()`` unless the step is to be skipped).  ``MMAD_GRAD_GUARD=<max_norm>`` (``inf``:
+measure and skip only) switches the guard on, with ``skip_nonfinite=True``, for a step built
+without either argument; unset, and without the arguments, ``guard`` is None and the captured
+graph holds exactly the kernels it held before.  Limits: the guard protects the parameters, both
+Adam moments, the step counters and the packed bf16 weights.  BatchNorm running statistics are
+written by the forward and are not rolled back: a backward-only overflow leaves them sound (the
+forward was finite), a non-finite *input* still poisons them.
+
 ``feed=`` (a device_cache.CacheFeed) puts the input pipeline into the graph as well: the
 captured body begins with ``feed.fetch_into(self.static)`` -- the fetch kernels read the
 epoch's order at a device cursor, then the cursor moves on -- so ``step()`` with no batch
@@ -192,14 +215,21 @@ class StagedBackward:
 
 class GraphedTrainStep:
     def __init__(self, model, optimizer, batch=None, warmup=3, reducer=None,
-                 collectives="inside", cuts=DEFAULT_CUTS, feed=None):
+                 collectives="inside", cuts=DEFAULT_CUTS, feed=None, clip_grad_norm=None,
+                 skip_nonfinite=False):
         """``reducer``: a data_parallel.GradAllReduce (for ``collectives="staged"`` built
         with ``stages=backward_stages(model, cuts)[1]``).  ``collectives``: see the module
         docstring.  ``feed``: a device_cache.CacheFeed whose fetch opens the captured step
-        (``batch`` may then be None)."""
+        (``batch`` may then be None).  ``clip_grad_norm`` (a max L2 norm) / ``skip_nonfinite``:
+        either one puts a gradient guard (``self.guard``, module docstring) in front of the
+        captured Adam; it needs the fused optimizer path and raises ``ValueError`` without
+        it."""
         self.model, self.optimizer = model, optimizer
         self.reducer = reducer
         self.feed = feed
+        guard = fused_optim.guard_settings(clip_grad_norm, skip_nonfinite,
+                                           fused_optim.GRAD_GUARD)
+        self.guard = None
         if feed is not None:
             feed.prepare()                   # device state + first kernel launches, pre-capture
             if batch is None:
@@ -216,6 +246,16 @@ class GraphedTrainStep:
             g["capturable"] = True
             if not torch.is_tensor(g["lr"]):
                 g["lr"] = torch.tensor(float(g["lr"]), dtype=torch.float32, device=dev)
+        if guard is not None:
+            if not fused_optim.supported(optimizer):
+                raise ValueError(
+                    "clip_grad_norm / skip_nonfinite need the fused optimizer step "
+                    "(fused_optim.AdamRepack): " +
+                    ("it is switched off (MMAD_ADAM_REPACK=0)" if not fused_optim.ENABLED else
+                     "this optimizer is not one it supports (torch.optim.Adam, fused=True, "
+                     "no amsgrad / maximize / grad scaler)"))
+            self.guard = fused_optim.GradGuard(optimizer, guard[0], guard[1])
+            self.guard.prepare(dev)
         staged = None
         if self.mode == "staged":
             bounds, params = backward_stages(model, cuts)
@@ -239,8 +279,13 @@ class GraphedTrainStep:
         # Adam fused with the weight repack (fused_optim): the captured forwards skip the
         # dual-layout repack, which the captured optimizer step writes for the next replay
         self.fused = None
+        if self.guard is not None and not fused_optim.state_ready(optimizer):
+            raise ValueError("clip_grad_norm / skip_nonfinite need the fused optimizer step, "
+                             "and the optimizer has no Adam state yet: use warmup >= 1 or run "
+                             "one eager step first")
         if fused_optim.supported(optimizer) and fused_optim.state_ready(optimizer):
-            self.fused = fused_optim.AdamRepack(optimizer, fused_optim.pack_plans(model))
+            self.fused = fused_optim.AdamRepack(optimizer, fused_optim.pack_plans(model),
+                                                guard=self.guard)
             self.fused.prepare(dev)
             self.fused.set_external(True)
         try:
@@ -343,7 +388,15 @@ class GraphedTrainStep:
         loss.backward()
         if self.reducer is not None:
             self.reducer.finish()
-        self.optimizer.step()
+        if self.guard is None:
+            self.optimizer.step()
+        else:
+            # the eager form of the guarded step: same kernels, the gradients clipped in place,
+            # and a host read of the skip flag (fine here, not in a replay)
+            self.guard.measure()
+            self.guard.apply_()
+            if not self.guard.stats()["skip"]:
+                self.optimizer.step()
         return loss.detach()
 
     def __call__(self, batch=None):
