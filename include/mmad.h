@@ -541,6 +541,50 @@ int mmad_bootstrap_cls_metrics(int n, int c, const double* logits, const int64_t
                                void* stream);
 int mmad_mean_std(int n, const float* v, double* out, void* stream);
 
+/* ---- epoch meter (csrc/meter.hip, metrics.EpochMeter) -------------------------------------
+ * The per-epoch numbers of Base_Model's *_epoch_end hooks (pkg/models/base_model.py:91-149:
+ * {split}_loss_epoch = torch.stack([x['loss'] for x in outputs]).mean(), a mean over BATCHES;
+ * {split}_f1_epoch / _class_{i} = MulticlassF1Score(average='macro' / 'none').compute()) and
+ * the rows that test_epoch_end concatenates for bootstrap_metric (:151-174), accumulated on the
+ * device by one one-block launch per step: no host read, no per-step .cpu() as the torchmetrics
+ * update does, capturable.  `state` is 8 + c * c eight-byte slots (8-byte aligned):
+ *   [0] seen        int64  rows offered (+= b on every update)
+ *   [1] counted     int64  rows counted (+= valid); also the next free row of the tables
+ *   [2] batches     int64  updates with valid > 0
+ *   [3] limit       int64  rows to count in all (caller; negative: no limit)
+ *   [4] bad_labels  int64  counted rows whose label lies outside [0, c)
+ *   [5] overflow    int64  counted rows that found the tables full
+ *   [6] loss_sum    double sum of the batch losses, in update order
+ *   [7] loss_last   double the last batch loss added
+ *   [8 + t * c + p] int64  confusion matrix, rows = target, columns = prediction
+ * Everything but [3] starts at zero (the caller zeroes it) and is written by the launches only.
+ *
+ * mmad_meter_update: logits [b][c] MMAD_F32 or MMAD_F64 (widened exactly), labels [b] int64.
+ *   valid = limit < 0 ? b : clamp(limit - seen, 0, b); only rows r < valid count, so the padded
+ *   tail of a full-shape last batch is ignored without the host knowing which launch is the last.
+ *   Prediction = argmax of the f64 row, first index on ties, a NaN wins (torch.argmax, the rule
+ *   of mmad_bootstrap_cls_metrics).  A label outside [0, c) adds to bad_labels and enters
+ *   neither the matrix nor the loss.  The matrix is counted in LDS with integer adds and added
+ *   to the state by the single block.  Batch loss: *loss_in when loss_in != NULL and valid == b;
+ *   otherwise, when valid > 0, the criterion of mmad_loss_fwd_ex (mode 0 weighted CE with `w`
+ *   (may be NULL), mode 1 focal with `gamma`) over rows 0 .. valid - 1, bit for bit the value
+ *   mmad_loss_fwd_ex gives for those rows; mode -1 (no criterion) makes that loss a NaN.  Then
+ *   loss_sum += loss, loss_last = loss, ++batches.  rows_logits [cap][c] double / rows_labels
+ *   [cap] int64 (both or neither): counted row r lands at index counted_before + r; rows at or
+ *   past cap are dropped and add to overflow.  c <= 16 (else MMAD_EBADSHAPE); pointers aligned
+ *   to their elements.
+ * mmad_meter_compute: out[0 .. 3 + c] (double) = mean batch loss loss_sum / batches (NaN with no
+ *   batch); torchmetrics-0.10 macro F1 (functional/classification/f_beta.py: classes with
+ *   tp + fp + fn = 0 left out of the mean, 0 when none is left); multiclass Matthews
+ *   correlation (functional/classification/matthews_corrcoef.py: 0 when a marginal is
+ *   degenerate); accuracy trace / total (0 for an empty matrix); per-class F1 2tp / (2tp + fp +
+ *   fn), 0 for an absent class.  All in f64 -- the definitions of mmad_bootstrap_cls_metrics. */
+int mmad_meter_update(int b, int c, int logits_dtype, const void* logits, const int64_t* labels,
+                      const double* loss_in, const double* w, double gamma, int mode,
+                      void* state, double* rows_logits, int64_t* rows_labels, int64_t cap,
+                      void* stream);
+int mmad_meter_compute(int c, const void* state, double* out, void* stream);
+
 /* ---- input pipeline normalisation (float64, batched over scans) -------------------
  * Replaces MultiModalDataset.__getitem__'s per-sample CPU normalisation
  * (pkg/utils/dataloader.py:213-215 PET, :244-270 MRI per-scan, :272-277 MRI all-scan).

@@ -6,7 +6,7 @@ weighted-CE loss, as hand-written HIP kernels behind the C ABI in include/mmad.h
 LightningModule classes (see classifiers.py) and the MedicalNet API (medicalnet.py).
 """
 from . import (_lib, augment, device_cache, explain, head_ops, layers, medicalnet,  # noqa: F401
-               preprocess, tabular, volume_ops)
+               metrics, preprocess, tabular, volume_ops)
 from .classifiers import (All_Modalities_Fusion, Anat_CNN, Anat_PET_CNN, Base_Model,  # noqa
                           FocalLoss, PET_CNN_ResNet, PET_MRI_EF, PET_MRI_FMF,
                           PET_MRI_ResNet_Fusion, PET_TABULAR_CNN,

@@ -201,6 +201,9 @@ _SIGS = {
     "mmad_max2_bwd": (_i32, [_i32, _i64, _vp, _vp, _vp, _vp, _vp]),
     "mmad_bootstrap_cls_metrics": (_i32, [_i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp]),
     "mmad_mean_std": (_i32, [_i32, _vp, _vp, _vp]),
+    "mmad_meter_update": (_i32, [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _f64, _i32, _vp, _vp, _vp,
+                                 _i64, _vp]),
+    "mmad_meter_compute": (_i32, [_i32, _vp, _vp, _vp]),
     "mmad_bn_relu_bwd_reduce": (_i32, [_i32, _i64, _i32] + [_vp] * 8),
     "mmad_bn_relu_bwd_apply": (_i32, [_i32, _i64, _i32] + [_vp] * 9),
     "mmad_augment_draw": (_i32, [_i32, _i32, _i32, _i32, C.POINTER(AugmentCfg), _vp, _vp, _vp,

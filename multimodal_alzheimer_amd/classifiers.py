@@ -205,6 +205,38 @@ class Base_Model(LightningModule, ABC):
             MulticlassMatthewsCorrCoef(num_classes=nc), y_hat, y)
         self.log_dict(d)
 
+    def epoch_metrics(self, meter_or_result, split):
+        """The dict ``_epoch_end(outputs, split)`` returns, from a metrics.EpochMeter that
+        watched the epoch's captured steps instead of the torchmetrics objects and the list of
+        step outputs: ``{split}_loss_epoch`` (the mean over batches, float64),
+        ``{split}_f1_epoch`` and ``{split}_f1_epoch_class_{i}`` (float32, as
+        ``metric.compute()`` gives them), ``step``, and additionally ``{split}_mcc_epoch``.
+        Takes the meter, a ``meter.snapshot()`` or that snapshot's ``result()``; for a meter the
+        snapshot is taken and waited for here -- the one host read of the epoch."""
+        res = meter_or_result
+        if hasattr(res, "snapshot"):
+            res = res.snapshot()
+        if hasattr(res, "result"):
+            res = res.result()
+        d = {f"{split}_loss_epoch": res["loss"], f"{split}_f1_epoch": res["f1"].float(),
+             "step": float(self.current_epoch)}
+        for i in range(self.hparams["n_classes"]):
+            d[f"{split}_f1_epoch_class_{i}"] = res["f1_per_class"][i].float()
+        d[f"{split}_mcc_epoch"] = res["mcc"].float()
+        return d
+
+    def test_metrics(self, meter):
+        """``epoch_metrics(meter, "test")`` plus the bootstrap entries of ``test_epoch_end``,
+        drawn by :meth:`bootstrap_metric` from the rows the meter kept (``keep_rows``)."""
+        d = self.epoch_metrics(meter, "test")
+        y_hat, y = meter.rows()
+        nc = self.hparams["n_classes"]
+        d["test_f1_epoch_boot"], d["test_f1_epoch_ci"] = self.bootstrap_metric(
+            MulticlassF1Score(num_classes=nc, average="macro"), y_hat, y)
+        d["test_mcc_epoch_boot"], d["test_mcc_epoch_ci"] = self.bootstrap_metric(
+            MulticlassMatthewsCorrCoef(num_classes=nc), y_hat, y)
+        return d
+
     def bootstrap_metric(self, metric, y_hat, y_labels, n_drawings=1000):
         """base_model.py:219-239: mean and 1.96*std over n_drawings resamples.
 

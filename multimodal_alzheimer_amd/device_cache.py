@@ -488,8 +488,9 @@ class DeviceVolumeCache:
         device: a diagnostic, not part of the step)"""
         return bool(self._bad.item())
 
-    def feed(self, batch_size, rank=0, world=1, shuffle=True, seed=15, drop_last=True):
-        return CacheFeed(self, batch_size, rank, world, shuffle, seed, drop_last)
+    def feed(self, batch_size, rank=0, world=1, shuffle=True, seed=15, drop_last=True,
+             pad_last=False):
+        return CacheFeed(self, batch_size, rank, world, shuffle, seed, drop_last, pad_last)
 
 
 class CacheFeed:
@@ -508,10 +509,19 @@ class CacheFeed:
       :meth:`before_replay` ahead of every replay, which rolls the epoch over when the
       previous one is used up.
 
-    The device state is created on first use; :meth:`epoch_order` / :meth:`epoch_batches` are
-    host-only."""
+    ``drop_last=False, pad_last=True`` gives full-shape batches over a ragged epoch, for a
+    captured evaluation that must see every sample: the device order is padded to
+    ``steps_per_epoch * batch_size`` entries by repeating the epoch's last index (every fetch
+    stays in range), :meth:`fetch_into` is allowed, and :attr:`valid_rows` says how many of the
+    epoch's rows are real -- the ``limit`` of a ``metrics.EpochMeter``, which ignores the rest.
+    The eager paths (:meth:`next_batch`, iteration, :meth:`epoch_batches`) are unchanged: their
+    last batch is short.
 
-    def __init__(self, cache, batch_size, rank=0, world=1, shuffle=True, seed=15, drop_last=True):
+    The device state is created on first use; :meth:`epoch_order` / :meth:`epoch_batches` /
+    :meth:`padded_order` are host-only."""
+
+    def __init__(self, cache, batch_size, rank=0, world=1, shuffle=True, seed=15, drop_last=True,
+                 pad_last=False):
         batch_size, rank, world = int(batch_size), int(rank), int(world)
         if batch_size <= 0:
             raise ValueError("batch_size must be positive")
@@ -520,6 +530,10 @@ class CacheFeed:
         self.cache, self.n = cache, int(cache.n)
         self.batch_size, self.rank, self.world = batch_size, rank, world
         self.shuffle, self.seed, self.drop_last = bool(shuffle), int(seed), bool(drop_last)
+        self.pad_last = bool(pad_last)
+        if self.pad_last and self.drop_last:
+            raise ValueError("pad_last pads the short last batch that drop_last=True drops: "
+                             "pass drop_last=False with it")
         self.per_rank = -(-self.n // world)
         self.steps_per_epoch = (self.per_rank // batch_size if drop_last
                                 else -(-self.per_rank // batch_size))
@@ -542,17 +556,33 @@ class CacheFeed:
     def __len__(self):
         return self.steps_per_epoch
 
+    @property
+    def valid_rows(self):
+        """the samples one epoch of this feed delivers (padding rows of ``pad_last`` left out)"""
+        return self.steps_per_epoch * self.batch_size if self.drop_last else self.per_rank
+
+    @property
+    def order_len(self):
+        """entries of the device order"""
+        return self.steps_per_epoch * self.batch_size if self.pad_last else self.per_rank
+
+    def padded_order(self, epoch):
+        """the device order of ``epoch``: :meth:`epoch_order`, with ``pad_last`` followed by
+        repeats of its last index up to ``steps_per_epoch * batch_size`` entries"""
+        o = list(self.epoch_order(epoch))
+        return o + o[-1:] * (self.order_len - len(o))
+
     # ----------------------------------------------------------------------- device side
     def _ensure(self):
         if self._order is None:
             dev = self.cache.device
-            self._order = torch.empty(self.per_rank, dtype=torch.int64, device=dev)
+            self._order = torch.empty(self.order_len, dtype=torch.int64, device=dev)
             self._cursor = torch.zeros((), dtype=torch.int64, device=dev)
             self._scratch = self.cache._scratch(self.batch_size)
             self._upload()
 
     def _upload(self):
-        host = torch.tensor(self.epoch_order(self.epoch), dtype=torch.int64).pin_memory()
+        host = torch.tensor(self.padded_order(self.epoch), dtype=torch.int64).pin_memory()
         # stream-ordered behind the fetches of the epoch before; the pinned block goes back to
         # torch's host allocator, which reuses it only after this copy has run
         self._order.copy_(host, non_blocking=True)
@@ -595,8 +625,9 @@ class CacheFeed:
         ``cache.empty_batch(batch_size)``) and advance the device cursor.  Capturable: under
         stream capture only the launches are recorded, and every replay is announced with
         :meth:`before_replay`; run eagerly, the call counts as a step itself."""
-        if not self.drop_last and self.per_rank % self.batch_size:
-            raise ValueError("fetch_into needs full batches: build the feed with drop_last=True")
+        if not self.drop_last and not self.pad_last and self.per_rank % self.batch_size:
+            raise ValueError("fetch_into needs full batches: build the feed with drop_last=True "
+                             "(or drop_last=False, pad_last=True)")
         capturing = torch.cuda.is_current_stream_capturing()
         if capturing and self._order is None:
             raise RuntimeError("call feed.prepare() before capturing fetch_into")

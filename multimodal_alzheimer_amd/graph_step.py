@@ -70,6 +70,15 @@ Adam moments, the step counters and the packed bf16 weights.  BatchNorm running 
 written by the forward and are not rolled back: a backward-only overflow leaves them sound (the
 forward was finite), a non-finite *input* still poisons them.
 
+``meter=`` (a metrics.EpochMeter) puts the epoch's bookkeeping into the graph: one one-block
+launch right after ``general_step`` folds the step's f64 logits, labels and loss into the meter's
+device state (confusion matrix, loss sum, counters), so a loop of replays ends with the numbers of
+``Base_Model._epoch_end`` on the device and not one host read; ``meter.snapshot()`` fetches them
+behind an event while the next epoch replays, ``meter.reset()`` starts the next epoch.  The eager
+warm-up steps do not update the meter (with a feed the first replay trains on the warm-up batch
+again, and it must count once).  Without ``meter`` the graph holds exactly the launches it held
+before.
+
 ``feed=`` (a device_cache.CacheFeed) puts the input pipeline into the graph as well: the
 captured body begins with ``feed.fetch_into(self.static)`` -- the fetch kernels read the
 epoch's order at a device cursor, then the cursor moves on -- so ``step()`` with no batch
@@ -81,6 +90,9 @@ counts steps on the host, uploads the next epoch's order between replays.  Under
 :class:`GraphedEvalForward` is the inference twin: an eval-mode ``general_step(..., "pred")``
 over a static batch with optional captured launches before and after it, no optimizer and no
 backward.  ``explain.occlusion`` replays it hundreds of times per explained batch.
+
+:class:`GraphedEvalEpoch` is a whole validation / test epoch on it: a feed's fetch, the eval
+forward and a meter's update in one graph, replayed ``len(feed)`` times with no host read.
 """
 import os
 
@@ -216,15 +228,17 @@ class StagedBackward:
 class GraphedTrainStep:
     def __init__(self, model, optimizer, batch=None, warmup=3, reducer=None,
                  collectives="inside", cuts=DEFAULT_CUTS, feed=None, clip_grad_norm=None,
-                 skip_nonfinite=False):
+                 skip_nonfinite=False, meter=None):
         """``reducer``: a data_parallel.GradAllReduce (for ``collectives="staged"`` built
         with ``stages=backward_stages(model, cuts)[1]``).  ``collectives``: see the module
         docstring.  ``feed``: a device_cache.CacheFeed whose fetch opens the captured step
         (``batch`` may then be None).  ``clip_grad_norm`` (a max L2 norm) / ``skip_nonfinite``:
         either one puts a gradient guard (``self.guard``, module docstring) in front of the
         captured Adam; it needs the fused optimizer path and raises ``ValueError`` without
-        it."""
+        it.  ``meter``: a metrics.EpochMeter that every replay updates with the step's f64
+        logits, labels and loss (module docstring)."""
         self.model, self.optimizer = model, optimizer
+        self.meter = meter
         self.reducer = reducer
         self.feed = feed
         guard = fused_optim.guard_settings(clip_grad_norm, skip_nonfinite,
@@ -242,6 +256,10 @@ class GraphedTrainStep:
         self.finish_events = None            # list: (start, end) events around each finish()
         self.static = {k: v.clone() if torch.is_tensor(v) else v for k, v in batch.items()}
         dev = next(model.parameters()).device
+        if meter is not None:
+            # device state and label landing buffer now: nothing is allocated in the capture
+            meter.prepare()
+            meter.landing(len(self.static["label"]), self.static["label"].dtype)
         for g in optimizer.param_groups:
             g["capturable"] = True
             if not torch.is_tensor(g["lr"]):
@@ -337,7 +355,7 @@ class GraphedTrainStep:
                 if self.mode == "after":
                     g = torch.cuda.CUDAGraph()
                     with torch.cuda.graph(g, capture_error_mode=_CAPTURE_MODE):
-                        self.out = model.general_step(self._fetched(), 0, "train")
+                        self.out = self._forward(model)
                         self.out["loss"].backward(self._one)
                         volume_ops.flush_wgrad_reduce()
                     self.graphs.append(g)
@@ -346,7 +364,7 @@ class GraphedTrainStep:
                     try:
                         g = torch.cuda.CUDAGraph()
                         with torch.cuda.graph(g, capture_error_mode=_CAPTURE_MODE):
-                            self.out = model.general_step(self._fetched(), 0, "train")
+                            self.out = self._forward(model)
                             staged.run(0, self.out["loss"], self._one)
                     finally:
                         staged.disarm()
@@ -368,13 +386,21 @@ class GraphedTrainStep:
         else:
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g, capture_error_mode=_CAPTURE_MODE):
-                self.out = model.general_step(self._fetched(), 0, "train")
+                self.out = self._forward(model)
                 self.out["loss"].backward(self._one)
                 volume_ops.flush_wgrad_reduce()
                 if reducer is not None:
                     reducer.finish()
                 self._opt_step()
             self.graphs.append(g)
+
+    def _forward(self, model):
+        """the captured step's forward: ``general_step`` and, with a meter, its update launch
+        right behind it (in graph 0 under every ``collectives`` mode)"""
+        out = model.general_step(self._fetched(), 0, "train")
+        if self.meter is not None:
+            self.meter.update(out["outputs"].detach(), out["labels"], out["loss"].detach())
+        return out
 
     def _fetched(self):
         """the step's input buffers; with a feed, filled by its (captured) fetch first"""
@@ -511,3 +537,57 @@ class GraphedEvalForward:
                                "BN statistics): capture a new GraphedEvalForward")
         self.graph.replay()
         return self.out
+
+
+class GraphedEvalEpoch:
+    """A validation / test epoch as replays of one captured graph: ``feed.fetch_into`` (the next
+    batch, read at the feed's device cursor), the eval-mode ``general_step(..., "pred")`` and
+    ``meter.update(logits, labels)`` -- a :class:`GraphedEvalForward` with the fetch as its
+    ``before`` and the update as its ``after``.  No host read anywhere in the epoch.
+
+    ``feed``: a device_cache.CacheFeed, for a score over every sample built with
+    ``shuffle=False, drop_last=False, pad_last=True``: every batch has the full shape, the last
+    one padded with repeats of the last sample, and ``meter.reset(limit=feed.valid_rows)`` makes
+    the meter ignore the padding (the model is in eval mode: BatchNorm uses its running
+    statistics, so a padding row cannot touch a real row's logits).  ``meter``: a
+    metrics.EpochMeter built with the model's criterion -- an evaluation forward hands on no
+    loss, so the meter computes the criterion itself, over the valid rows only; a criterion
+    without ``fused_spec()`` raises ``ValueError`` here, before anything is captured.
+
+    :meth:`run` rewinds the feed to the start of epoch 0 (the same order on every run), resets
+    the meter to ``feed.valid_rows``, replays ``len(feed)`` times and returns
+    ``meter.snapshot()``; ``model.epoch_metrics(snapshot, "val")`` reads it.
+
+    The captured launches hold the folded eval weights (``volume_ops.conv_bn_act_eval``), and
+    the fold is keyed on ``volume_ops._BN_UPDATES``, which every training replay advances: after
+    training, :meth:`run` raises ``RuntimeError`` as :class:`GraphedEvalForward` does.  The
+    expected use is therefore one ``GraphedEvalEpoch`` per validation epoch, built after
+    ``model.eval()`` and dropped before ``model.train()``.  A build costs ``warmup`` eager
+    forwards (the first one refolds every conv's weights, one fold launch and one pack launch
+    per conv) plus the capture; the epoch itself is ``len(feed)`` graph launches, against
+    ``len(feed)`` times the forward's launch count issued from Python."""
+
+    def __init__(self, model, feed, meter, warmup=2):
+        if meter.spec is None:
+            tail = feed.valid_rows % feed.batch_size
+            raise ValueError(
+                "GraphedEvalEpoch: the meter computes the evaluation loss itself" +
+                (f", and the loss of the last batch's {tail} valid rows" if tail else "") +
+                ": build the EpochMeter with a criterion that has a fused_spec()")
+        self.model, self.feed, self.meter = model, feed, meter
+        feed.prepare()
+        meter.prepare()
+        static = feed.cache.empty_batch(feed.batch_size)
+        meter.landing(feed.batch_size, static["label"].dtype)
+        self.forward = GraphedEvalForward(
+            model, static, warmup=warmup, before=feed.fetch_into,
+            after=lambda out: meter.update(out, static["label"]))
+
+    def run(self):
+        """one epoch; returns the meter's snapshot (``.result()`` waits for it)"""
+        self.feed.set_epoch(0)
+        self.meter.reset(limit=self.feed.valid_rows)
+        for _ in range(len(self.feed)):
+            self.feed.before_replay()
+            self.forward()
+        return self.meter.snapshot()
